@@ -126,3 +126,16 @@ def build_pytorch_app() -> Model:
 @pytest.fixture
 def pytorch_model() -> Model:
     return build_pytorch_app()
+
+
+@pytest.fixture
+def gloo_cpu_only(monkeypatch):
+    """Pin a multi-process gloo/CPU test to the CPU on machines that have
+    GPUs too: spawned ranks inherit an empty device list, and this process
+    reports none, so ``dp`` is not capped by the number of visible GPUs."""
+    import torch
+
+    monkeypatch.setenv("HIP_VISIBLE_DEVICES", "")
+    monkeypatch.setenv("CUDA_VISIBLE_DEVICES", "")
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
+    monkeypatch.setattr(torch.cuda, "device_count", lambda: 0)

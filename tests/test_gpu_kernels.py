@@ -188,6 +188,51 @@ def test_step_fused_matches_stepwise(ext, dev):
     assert abs(loss_out.item() - a_loss) < 1e-3
 
 
+def test_step_kernels_reproducible_bitwise(ext, dev):
+    """The same steps from the same state give the same bits every time:
+    bias grads and loss are summed over waves in a fixed order (no float
+    atomics), slabs over workgroups likewise. Fused step on 8 workgroups
+    with a ragged tail, and the persistent multi-chunk kernel."""
+    from unionml_amd.ops import reference as ref
+    from unionml_amd.ops.tabular import ADAM_BETA1, ADAM_BETA2, ADAM_EPS, TabularMLP
+
+    torch.manual_seed(33)
+    B, n_steps = 1000, 40
+    Xbf = (torch.randn(B, 64) * 1.2).bfloat16().to(dev)
+    y = torch.randint(0, 10, (B,), dtype=torch.int32, device=dev)
+    Bp, Np = 256, 512   # persistent kernel: 2 chunks per step, 2 batches
+    Xp = (torch.randn(Np, 64) * 1.2).bfloat16().to(dev)
+    yp = torch.randint(0, 10, (Np,), dtype=torch.int32, device=dev)
+
+    def run_fused():
+        c = TabularMLP(device=dev, seed=6)
+        c._ensure_slabs((B + 127) // 128)
+        loss_out = c.grads[ref.NPARAM : ref.NPARAM + 1]
+        for _ in range(n_steps):
+            assert ext.mlp_step_fused(Xbf, y, c.W1bf, c.W2bf, c.master, c.bfmirror,
+                                      c.m, c.v, c.t_dev, c.slabs, c.counter, loss_out,
+                                      1.0 / B, 1e-3, ADAM_BETA1, ADAM_BETA2, ADAM_EPS)
+        torch.cuda.synchronize()
+        return [t.clone() for t in (c.master, c.m, c.v, c.bfmirror, loss_out)]
+
+    def run_persistent():
+        c = TabularMLP(device=dev, seed=6)
+        loss_out = c.grads[ref.NPARAM : ref.NPARAM + 1]
+        assert ext.mlp_train_steps(Xp, yp, Bp, n_steps, c.master, c.bfmirror, c.m, c.v,
+                                   c.t_dev, loss_out, 1e-3, ADAM_BETA1, ADAM_BETA2,
+                                   ADAM_EPS)
+        torch.cuda.synchronize()
+        return [t.clone() for t in (c.master, c.m, c.v, loss_out)]
+
+    for run in (run_fused, run_persistent):
+        first = run()
+        assert all(torch.isfinite(t.float()).all() for t in first)
+        for _ in range(2):
+            again = run()
+            for t0, t1 in zip(first, again):
+                assert torch.equal(t0, t1), f"{run.__name__}: not bit-identical"
+
+
 def test_train_digits_gpu_accuracy(ext, dev):
     from sklearn.datasets import load_digits
 

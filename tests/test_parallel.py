@@ -104,7 +104,7 @@ def test_gradient_allreducer_world2(tmp_path):
     assert (tmp_path / "ok_0").exists() and (tmp_path / "ok_1").exists()
 
 
-def test_model_train_dp2():
+def test_model_train_dp2(gloo_cpu_only):
     """Model.train(dp=2) spawns 2 gloo ranks, shards the train split, and
     returns a rank-0 artifact."""
     from dp_app import model
@@ -222,7 +222,7 @@ def test_reducer_partial_bucket_world2(tmp_path):
     assert (tmp_path / "ok_0").exists() and (tmp_path / "ok_1").exists()
 
 
-def test_dp_worker_failure_surfaces_clean_error():
+def test_dp_worker_failure_surfaces_clean_error(gloo_cpu_only):
     """A trainer crashing inside a DP worker must surface as a
     RuntimeError with the worker traceback, not a hang."""
     from dp_app import build_failing_model

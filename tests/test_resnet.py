@@ -55,7 +55,7 @@ def test_resnet_single_image_feature_loader():
 
 
 @pytest.mark.timeout(300)
-def test_resnet_dp2_trains_on_cpu():
+def test_resnet_dp2_trains_on_cpu(gloo_cpu_only):
     """dp=2 over gloo: spawn 2 ranks, shard rows, bucketed all-reduce;
     must produce a valid artifact (multi-process CPU proof of the
     generic DP path)."""

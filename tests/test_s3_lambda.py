@@ -6,6 +6,7 @@ docs/source/reacting_to_s3_events.md; here it is executable)."""
 import json
 import sys
 import types
+import uuid
 from pathlib import Path
 
 import pytest
@@ -19,10 +20,12 @@ runner = CliRunner()
 class _FakeS3:
     """In-memory bucket store honoring the two calls the handler makes."""
 
-    def __init__(self, store):
+    def __init__(self, store, downloaded):
         self.store = store
+        self.downloaded = downloaded
 
     def download_file(self, bucket, key, local):
+        self.downloaded.append(Path(local))
         Path(local).write_bytes(self.store[(bucket, key)])
 
     def put_object(self, Bucket, Key, Body):
@@ -36,8 +39,9 @@ def test_s3_event_handler_round_trip(tmp_path, monkeypatch):
     assert result.exit_code == 0, result.output
 
     store = {}
+    downloaded = []  # handler-side scratch copies, removed at the end
     boto3 = types.ModuleType("boto3")
-    boto3.client = lambda name: _FakeS3(store)
+    boto3.client = lambda name: _FakeS3(store, downloaded)
     monkeypatch.setitem(sys.modules, "boto3", boto3)
 
     sys.path.insert(0, str(tmp_path / "s3app"))
@@ -51,16 +55,19 @@ def test_s3_event_handler_round_trip(tmp_path, monkeypatch):
         s3_app.model.artifact = None
         monkeypatch.setenv("UNIONML_MODEL_PATH", str(artifact))
 
-        # an uploaded features file (JSON records of digit pixels)
+        # an uploaded features file (JSON records of digit pixels); the
+        # handler downloads it to /tmp/<basename of the key>, so the key is
+        # unique to this run and the copy is removed at the end
+        key = f"incoming/batch-{uuid.uuid4().hex}.json"
         feats = [{f"pixel_{r}_{c}": 0.0 for r in range(8) for c in range(8)}]
-        store[("my-bucket", "incoming/batch1.json")] = json.dumps(feats).encode()
+        store[("my-bucket", key)] = json.dumps(feats).encode()
 
         event = {
             "Records": [
                 {
                     "s3": {
                         "bucket": {"name": "my-bucket"},
-                        "object": {"key": "incoming/batch1.json"},
+                        "object": {"key": key},
                     }
                 }
             ]
@@ -69,8 +76,10 @@ def test_s3_event_handler_round_trip(tmp_path, monkeypatch):
         assert resp["statusCode"] == 200
         body = json.loads(resp["body"])
         assert body[0]["n"] == 1
-        out = json.loads(store[("my-bucket", "incoming/batch1.json.predictions.json")])
+        out = json.loads(store[("my-bucket", f"{key}.predictions.json")])
         assert len(out) == 1 and 0 <= out[0] <= 9
     finally:
+        for local in downloaded:
+            local.unlink(missing_ok=True)
         sys.path.remove(str(tmp_path / "s3app"))
         sys.modules.pop("app", None)

@@ -219,7 +219,11 @@ standardize_apply_kernel(const float* __restrict__ X, long long n_elems, int D,
 #define C_LOSS ALIGN16(C_DB2 + CPAD * 4)
 #define C_B1S  ALIGN16(C_LOSS + 16)
 #define C_B2S  ALIGN16(C_B1S + HID * 4)
-#define C_IMG_TOTAL ALIGN16(C_B2S + CPAD * 4)
+// per-wave bias-grad / loss partials of one chunk: [wave][HID + CPAD + 1]
+#define NWAVE  (BLOCK / 64)
+#define PART   (HID + CPAD + 1)
+#define C_PART ALIGN16(C_B2S + CPAD * 4)
+#define C_IMG_TOTAL ALIGN16(C_PART + NWAVE * PART * 4)
 // steps kernel appends optimizer state after the images:
 #define C_MASTER C_IMG_TOTAL
 #define C_M    ALIGN16(C_MASTER + NPARAM * 4)
@@ -242,6 +246,7 @@ struct Lds {
   float* loss;
   float* b1s;   // bias prefetch (fwd chain must not stall on cold HBM)
   float* b2s;
+  float* part;  // [NWAVE][PART]: db1 | db2 | loss, one row per wave
 };
 
 __device__ __forceinline__ Lds carve(char* smem) {
@@ -261,6 +266,7 @@ __device__ __forceinline__ Lds carve(char* smem) {
   L.loss = (float*)(smem + C_LOSS);
   L.b1s = (float*)(smem + C_B1S);
   L.b2s = (float*)(smem + C_B2S);
+  L.part = (float*)(smem + C_PART);
   return L;
 }
 
@@ -443,8 +449,9 @@ __device__ __forceinline__ void chunk_fwd_bwd(
       if (valid && c == label) loss_acc = -(logit[r] - m - logs) * invBtot;
     }
     // reduce db2/loss over the 16 row-lanes (lr bits) first, then ONE
-    // LDS atomic per (wave, class) — the per-element atomic version
-    // serialized ~2048 adds onto 16 LDS addresses per workgroup
+    // plain store per (wave, class) into this wave's partial row: the
+    // waves are summed in fixed order below, so the step is reproducible
+    // bit for bit (float LDS atomics landed in arrival order)
     #pragma unroll
     for (int bit = 1; bit < 16; bit <<= 1) {
       #pragma unroll
@@ -453,13 +460,13 @@ __device__ __forceinline__ void chunk_fwd_bwd(
     }
     if (lr == 0) {
       #pragma unroll
-      for (int r = 0; r < 4; ++r) atomicAdd(&L.db2[lg * 4 + r], db2_acc[r]);
+      for (int r = 0; r < 4; ++r) L.part[wave * PART + HID + lg * 4 + r] = db2_acc[r];
     }
     // loss_acc now holds the 16-row sum within this lg quarter; fold
-    // the four lg groups (lane bits 4,5) too, then one atomic per wave
+    // the four lg groups (lane bits 4,5) too, then one store per wave
     loss_acc += __shfl_xor(loss_acc, 16, 64);
     loss_acc += __shfl_xor(loss_acc, 32, 64);
-    if (l == 0) atomicAdd(L.loss, loss_acc);
+    if (l == 0) L.part[wave * PART + HID + CPAD] = loss_acc;
   }
   // NO __syncthreads here either: dH reads only this wave's rows of
   // DLs and HT. Cross-wave consumers (dW1/dW2 over DLT/HT) wait at the
@@ -485,10 +492,21 @@ __device__ __forceinline__ void chunk_fwd_bwd(
       dh += __shfl_xor(dh, 2, 64);
       dh += __shfl_xor(dh, 4, 64);
       dh += __shfl_xor(dh, 8, 64);
-      if (lr == 0) atomicAdd(&L.db1[h], dh);
+      if (lr == 0) L.part[wave * PART + h] = dh;
     }
   }
-  __syncthreads();   // DHT complete
+  __syncthreads();   // DHT + per-wave partials complete
+
+  // ---- db1/db2/loss += partials, waves in fixed order. The last wave does
+  // it: it has no dW2 tile, so this stays off the longest wave's path ----
+  if (wave == NWAVE - 1 && l < PART) {
+    float sum = 0.f;
+    #pragma unroll
+    for (int w = 0; w < NWAVE; ++w) sum += L.part[w * PART + l];
+    if (l < HID) L.db1[l] += sum;
+    else if (l < HID + CPAD) L.db2[l - HID] += sum;
+    else L.loss[0] += sum;
+  }
 
   // ---- dW1^T += DHT @ B(XT): wave tile (ht = w&1, it = w>>1) ---------------
   {
