@@ -17,16 +17,16 @@
 int main(int argc, char** argv) {
   const int B = argc > 1 ? atoi(argv[1]) : 2048;
   const int iters = argc > 2 ? atoi(argv[2]) : 2000;
-  const int n_wg = (B + 127) / 128;
+  const int n_wg = (B + ROWS - 1) / ROWS;
 
   unsigned short *Xbf, *W1bf, *W2bf, *bfmirror;
   int *y, *t_dev;
   unsigned* counter;
   float *master, *m, *v, *slabs, *loss;
   unsigned short* wimg;
-  CHECK(hipMalloc(&Xbf, (size_t)B * 64 * 2));
-  CHECK(hipMalloc(&W1bf, 64 * 32 * 2));
-  CHECK(hipMalloc(&W2bf, 32 * 16 * 2));
+  CHECK(hipMalloc(&Xbf, (size_t)B * IN * 2));
+  CHECK(hipMalloc(&W1bf, IN * HID * 2));
+  CHECK(hipMalloc(&W2bf, HID * CPAD * 2));
   CHECK(hipMalloc(&bfmirror, (NPARAM + 8) * 2));
   CHECK(hipMalloc(&y, (size_t)B * 4));
   CHECK(hipMalloc(&t_dev, 4));
@@ -36,11 +36,11 @@ int main(int argc, char** argv) {
   CHECK(hipMalloc(&v, NPARAM * 4));
   CHECK(hipMalloc(&slabs, (size_t)n_wg * SLAB * 4));
   CHECK(hipMalloc(&loss, 4));
-  CHECK(hipMalloc(&wimg, 4224 * 2));
-  CHECK(hipMemset(wimg, 0, 4224 * 2));
-  CHECK(hipMemset(Xbf, 0, (size_t)B * 64 * 2));
-  CHECK(hipMemset(W1bf, 0, 64 * 32 * 2));
-  CHECK(hipMemset(W2bf, 0, 32 * 16 * 2));
+  CHECK(hipMalloc(&wimg, DIGITS_WIMG_N * 2));
+  CHECK(hipMemset(wimg, 0, DIGITS_WIMG_N * 2));
+  CHECK(hipMemset(Xbf, 0, (size_t)B * IN * 2));
+  CHECK(hipMemset(W1bf, 0, IN * HID * 2));
+  CHECK(hipMemset(W2bf, 0, HID * CPAD * 2));
   CHECK(hipMemset(y, 0, (size_t)B * 4));
   CHECK(hipMemset(t_dev, 0, 4));
   CHECK(hipMemset(counter, 0, 4));

@@ -21,6 +21,11 @@ ext = CUDAExtension(
         "unionml_amd/ops/hip/tabular_kernels.hip",
         "unionml_amd/ops/hip/tabular_gen.hip",
     ],
+    # editing a shared header rebuilds the extension
+    depends=[
+        "unionml_amd/ops/hip/tabular_common.h",
+        "unionml_amd/ops/hip/tabular_launch.h",
+    ],
     extra_compile_args={
         "cxx": ["-O3", "-std=c++17"],
         "nvcc": ["-O3", "-std=c++17", "--offload-arch=gfx950"],

@@ -27,41 +27,21 @@
 //     kernel's G16 epoch-tag handshake is deliberately NOT used here
 //     (A/B trail: profiles/r02_gen_kernel_stats.md). MFMA
 //     __builtin_amdgcn_mfma_f32_16x16x32_bf16 with the
-//     hardware-verified fragment mapping documented in
-//     tabular_kernels.hip:34-46. Classes are runtime (<= 32, one or
-//     two MFMA tiles): the wave-shuffle softmax masks c >= cls and
-//     folds across the register-resident class-tile axis.
+//     hardware-verified fragment mapping documented in the header of
+//     tabular_kernels.hip. Classes are runtime (<= 32, one or two
+//     MFMA tiles): the wave-shuffle softmax (tabular_common.h head_*)
+//     masks c >= cls and folds across the register-resident
+//     class-tile axis.
 //
 // All launches are stream-ordered and hipGraph-capturable; the Adam
 // step counter lives in device memory so bias correction is exact
 // under graph replay.
 
 #include <hip/hip_runtime.h>
-#include <hip/hip_bf16.h>
 
-typedef __attribute__((ext_vector_type(8))) short bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef unsigned short u16;
+#include "tabular_common.h"
 
 namespace gen {
-
-__device__ __forceinline__ float bf2f(u16 v) {
-  union { float f; unsigned u; } c;
-  c.u = ((unsigned)v) << 16;
-  return c.f;
-}
-
-__device__ __forceinline__ u16 f2bf(float f) {
-  union { float f; unsigned u; } c;
-  c.f = f;
-  unsigned lsb = (c.u >> 16) & 1u;
-  c.u += 0x7fffu + lsb;  // round-to-nearest-even
-  return (u16)(c.u >> 16);
-}
-
-__device__ __forceinline__ float fast_rcp(float x) {
-  return __builtin_amdgcn_rcpf(x);
-}
 
 constexpr int A16(int x) { return (x + 15) & ~15; }
 constexpr int IMAX(int a, int b) { return a > b ? a : b; }
@@ -82,7 +62,7 @@ struct GG {
   static constexpr int BLOCK = WAVES * 64;
 
   // LDS row strides (u16 elems), +8 keeps b128 alignment w/ distinct
-  // bank slots per row (same scheme as tabular_kernels.hip:60-63)
+  // bank slots per row (same scheme as tabular_kernels.hip XS/HS/TS/WS)
   static constexpr int XSS = TK + 8;    // Xs tile   [RT][XSS]
   static constexpr int XTS = RT + 8;    // XT tile   [TK][XTS]   (shares xbuf)
   static constexpr int W1S = TK + 8;    // W1T tile  [HID][W1S]
@@ -187,30 +167,8 @@ struct GG {
   }
 };
 
-// packed global weight-image offsets (bf16 elems): W1Tg [HID][inp] then
-// W2sg [HID][32] (cols >= 16 zero) then W2Tg [16][HID]
-__device__ __forceinline__ int wimg_w2s_off(int hid, int inp) { return hid * inp; }
-__device__ __forceinline__ int wimg_w2t_off(int hid, int inp) {
-  return hid * inp + hid * 32;
-}
-
-// Adam-phase image maintenance: param i -> packed-image stores
-template <int HID, int CP>
-__device__ __forceinline__ void wimg_write_gen(u16* __restrict__ wimg, int inp,
-                                               int off_b1, int off_w2, int off_b2,
-                                               int i, u16 wb) {
-  if (i < off_b1) {                       // W1: i = in*HID + h
-    const int in = i / HID;
-    const int h = i % HID;
-    wimg[h * inp + in] = wb;
-  } else if (i >= off_w2 && i < off_b2) { // W2: j = h*CP + c
-    const int j = i - off_w2;
-    const int h = j / CP;
-    const int c = j % CP;
-    wimg[wimg_w2s_off(HID, inp) + h * 32 + c] = wb;
-    wimg[wimg_w2t_off(HID, inp) + c * HID + h] = wb;
-  }
-}
+// (packed global weight-image layout and its Adam-phase store:
+// tabular_common.h wimg_w2s_off / wimg_w2t_off / wimg_write_gen)
 
 // ---------------------------------------------------------------------------
 // cooperative LDS loaders (all BLOCK threads)
@@ -426,31 +384,10 @@ mlp_step_gen_kernel(const u16* __restrict__ Xbf,   // [N][inp] staged bf16 (zero
     const bool valid = (row0 + row) < (long long)B;
     const int label = valid ? y[row0 + row] : -1;
 
-    float logit[G::NCT][4];
-    float mx = -1e30f;
-    #pragma unroll
-    for (int ct = 0; ct < G::NCT; ++ct) {
-      #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int c = ct * 16 + lg * 4 + r;
-        logit[ct][r] = (c < cls) ? acc[ct][r] + L.b2s[c] : -1e30f;
-        mx = fmaxf(mx, logit[ct][r]);
-      }
-    }
-    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    float e[G::NCT][4], ssum = 0.f;
-    #pragma unroll
-    for (int ct = 0; ct < G::NCT; ++ct) {
-      #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int c = ct * 16 + lg * 4 + r;
-        e[ct][r] = (c < cls) ? __expf(logit[ct][r] - mx) : 0.f;
-        ssum += e[ct][r];
-      }
-    }
-    ssum += __shfl_xor(ssum, 16, 64);
-    ssum += __shfl_xor(ssum, 32, 64);
+    float logit[G::NCT][4], e[G::NCT][4];
+    head_logits<G::NCT>(logit, acc, L.b2s, cls, lg);
+    const float mx = head_row_max<G::NCT>(logit);
+    const float ssum = head_exp_sum<G::NCT>(e, logit, mx, cls, lg);
     const float rs = fast_rcp(ssum);
     const float logs = __logf(ssum);
     float db2_acc[G::NCT][4];
@@ -511,10 +448,7 @@ mlp_step_gen_kernel(const u16* __restrict__ Xbf,   // [N][inp] staged bf16 (zero
         const float hv = bf2f(L.HT[h][row]);
         float dh = hv > 0.f ? acc[r] : 0.f;
         L.DHT[h][row] = f2bf(dh);
-        dh += __shfl_xor(dh, 1, 64);
-        dh += __shfl_xor(dh, 2, 64);
-        dh += __shfl_xor(dh, 4, 64);
-        dh += __shfl_xor(dh, 8, 64);
+        dh = row_sum16(dh);
         if (lr_ == 0) atomicAdd(&L.db1[h], dh);
       }
     }
@@ -616,11 +550,8 @@ reduce_adam_gen_kernel(const float* __restrict__ slabs, int n_wg,
                        float* __restrict__ grads_out,
                        unsigned* __restrict__ done_counter) {
   const float t_new = (float)(*t_dev + 1);
-  const float corr1 = fast_rcp(1.f - __powf(beta1, t_new));
-  const float corr2 = fast_rcp(1.f - __powf(beta2, t_new));
-  const int off_b1 = inp * hid;
-  const int off_w2 = off_b1 + hid;
-  const int off_b2 = off_w2 + hid * cpad;
+  float corr1, corr2;
+  adam_bias_corr(beta1, beta2, t_new, corr1, corr2);
   for (int i = blockIdx.x * 256 + threadIdx.x; i <= nparam;
        i += gridDim.x * 256) {
     float g0 = 0.f, g1 = 0.f, g2 = 0.f, g3 = 0.f;
@@ -641,24 +572,14 @@ reduce_adam_gen_kernel(const float* __restrict__ slabs, int n_wg,
       *loss_out = g;
       continue;
     }
-    const float mi = beta1 * m[i] + (1.f - beta1) * g;
-    const float vi = beta2 * v[i] + (1.f - beta2) * g * g;
+    float p = master[i], mi = m[i], vi = v[i];
+    adam_update(p, mi, vi, g, lr, beta1, beta2, eps, corr1, corr2);
     m[i] = mi;
     v[i] = vi;
-    const float p = master[i] - lr * (mi * corr1) * fast_rcp(sqrtf(vi * corr2) + eps);
     master[i] = p;
     const u16 wb = f2bf(p);
     bfmirror[i] = wb;
-    if (wimg) {
-      if (i < off_b1) {
-        wimg[(i % hid) * inp + (i / hid)] = wb;
-      } else if (i >= off_w2 && i < off_b2) {
-        const int j = i - off_w2;
-        const int h = j / cpad, c = j % cpad;
-        wimg[hid * inp + h * 32 + c] = wb;
-        wimg[hid * inp + hid * 32 + c * hid + h] = wb;
-      }
-    }
+    if (wimg) wimg_write_gen(wimg, inp, hid, cpad, i, wb);
   }
   // advance the Adam step counter in-kernel: every WG read t_dev at
   // entry (the last-done WG writes only after all WGs passed their
@@ -775,40 +696,15 @@ mlp_predict_gen_kernel(const float* __restrict__ X,  // [B][draw] raw fp32
       }
     }
     const int row = t2 * 16 + lr;
-    float best = -1e30f;
-    int bcol = cls;
+    float best;
+    int bcol;
     float logit[G::NCT][4];
-    #pragma unroll
-    for (int ct = 0; ct < G::NCT; ++ct) {
-      #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int c = ct * 16 + lg * 4 + r;
-        logit[ct][r] = (c < cls) ? acc[ct][r] + L.b2s[c] : -1e30f;
-        // ties pick the lowest class (match torch.argmax)
-        if (logit[ct][r] > best) { best = logit[ct][r]; bcol = c; }
-      }
-    }
-    #pragma unroll
-    for (int d = 16; d < 64; d <<= 1) {
-      const float ov = __shfl_xor(best, d, 64);
-      const int oc = __shfl_xor(bcol, d, 64);
-      if (ov > best || (ov == best && oc < bcol)) { best = ov; bcol = oc; }
-    }
+    head_logits<G::NCT>(logit, acc, L.b2s, cls, lg);
+    head_argmax<G::NCT>(logit, cls, lg, best, bcol);
     if (lg == 0 && row0 + row < B) preds[row0 + row] = bcol;
     if (probs != nullptr) {
-      float ssum = 0.f, e[G::NCT][4];
-      #pragma unroll
-      for (int ct = 0; ct < G::NCT; ++ct) {
-        #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int c = ct * 16 + lg * 4 + r;
-          e[ct][r] = (c < cls) ? __expf(logit[ct][r] - best) : 0.f;
-          ssum += e[ct][r];
-        }
-      }
-      ssum += __shfl_xor(ssum, 16, 64);
-      ssum += __shfl_xor(ssum, 32, 64);
-      const float rs = fast_rcp(ssum);
+      float e[G::NCT][4];
+      const float rs = fast_rcp(head_exp_sum<G::NCT>(e, logit, best, cls, lg));
       #pragma unroll
       for (int ct = 0; ct < G::NCT; ++ct) {
         #pragma unroll
@@ -834,32 +730,17 @@ adam_step_gen_kernel(float* __restrict__ master, u16* __restrict__ bfmirror,
                      int nparam, int inp, int hid, int cpad,
                      float lr, float beta1, float beta2, float eps,
                      u16* __restrict__ wimg) {
-  const float t = (float)(*t_dev + 1);
-  const float corr1 = fast_rcp(1.f - __powf(beta1, t));
-  const float corr2 = fast_rcp(1.f - __powf(beta2, t));
-  const int off_b1 = inp * hid;
-  const int off_w2 = off_b1 + hid;
-  const int off_b2 = off_w2 + hid * cpad;
+  float corr1, corr2;
+  adam_bias_corr(beta1, beta2, (float)(*t_dev + 1), corr1, corr2);
   for (int i = blockIdx.x * 256 + threadIdx.x; i < nparam; i += gridDim.x * 256) {
-    const float g = grads[i];
-    const float mi = beta1 * m[i] + (1.f - beta1) * g;
-    const float vi = beta2 * v[i] + (1.f - beta2) * g * g;
+    float p = master[i], mi = m[i], vi = v[i];
+    adam_update(p, mi, vi, grads[i], lr, beta1, beta2, eps, corr1, corr2);
     m[i] = mi;
     v[i] = vi;
-    const float p = master[i] - lr * (mi * corr1) * fast_rcp(sqrtf(vi * corr2) + eps);
     master[i] = p;
     const u16 wb = f2bf(p);
     bfmirror[i] = wb;
-    if (wimg) {
-      if (i < off_b1) {
-        wimg[(i % hid) * inp + (i / hid)] = wb;
-      } else if (i >= off_w2 && i < off_b2) {
-        const int j = i - off_w2;
-        const int h = j / cpad, c = j % cpad;
-        wimg[hid * inp + h * 32 + c] = wb;
-        wimg[hid * inp + hid * 32 + c * hid + h] = wb;
-      }
-    }
+    if (wimg) wimg_write_gen(wimg, inp, hid, cpad, i, wb);
   }
 }
 
@@ -872,16 +753,6 @@ __global__ void bump_t_kernel(int* __restrict__ t_dev) { ++(*t_dev); }
 // ---------------------------------------------------------------------------
 
 namespace {
-
-int rt_for_hid(int hid) {
-  switch (hid) {
-    case 32: return 128;
-    case 64: return 128;
-    case 128: return 64;
-    case 256: return 32;
-  }
-  return 0;
-}
 
 template <int HID, int RT, int CP>
 int launch_step_gen_t(const unsigned short* Xbf, const int* y, int B, int inp,
@@ -931,9 +802,6 @@ int launch_predict_gen_t(const float* X, int B, int draw, int inp, int cls,
 }  // namespace
 
 extern "C" {
-
-// supported hidden widths (template instantiations); returns rows/WG or 0
-int gen_rt_for_hid(int hid) { return rt_for_hid(hid); }
 
 int launch_mlp_step_gen(const unsigned short* Xbf, const int* y, int B, int inp,
                         int hid, int cls, int rt, const unsigned short* wimg,

@@ -4,10 +4,16 @@
 // unionai-oss/unionml is pure Python and has no kernels):
 //   - standardize_fit / standardize_apply : per-column (x-mean)*invstd, fp32 -> bf16
 //   - mlp_step        : fused fwd+bwd of the digits MLP
-//                       (IN=64 -> HID=32 relu -> CLS=10 softmax/xent) producing
-//                       fp32 grads + loss in ONE launch (DP path: the RCCL
-//                       all-reduce of the 2.6k-float grad buffer sits between
-//                       this and adam_step)
+//                       (IN=64 -> HID=32 relu -> CLS=10 softmax/xent) adding
+//                       fp32 grads + loss onto a zeroed buffer with global
+//                       atomics. No training path launches it; only the
+//                       kernel tests and benchmarks/probe_steps.py do.
+//   - mlp_step_fused  : fwd+bwd + cross-workgroup slab reduction + Adam in
+//                       ONE launch (the default single-GPU engine). With
+//                       grads_out it stops after the reduction: that is the
+//                       DP path and the benchmark's stepwise engine, where
+//                       the RCCL all-reduce of the 2.6k-float grad buffer
+//                       sits between it and adam_step
 //   - adam_step       : single-block fused Adam on the flat fp32 master
 //   - mlp_train_steps : single-GPU flagship — a persistent single-workgroup
 //                       kernel running N optimizer steps in ONE launch with
@@ -46,43 +52,21 @@
 // graph replay.
 
 #include <hip/hip_runtime.h>
-#include <hip/hip_bf16.h>
 
-#define IN 64
-#define HID 32
-#define CLS 10
-#define CPAD 16          // CLS padded to one MFMA tile
+#include "tabular_common.h"
+
+// short names for the digits layout (defined once, in tabular_launch.h)
+constexpr int IN = DIGITS_IN, HID = DIGITS_HID, CLS = DIGITS_CLS;
+constexpr int CPAD = DIGITS_CPAD;   // CLS padded to one MFMA tile
 #define ROWS 128         // batch rows per workgroup / per chunk
 #define WAVES 8
 #define BLOCK (WAVES * 64)
 
 // LDS strides in bf16 elements (row-major [rows][stride]):
-#define XS 72            // Xs  [ROWS][72]  (144 B rows)
+constexpr int XS = DIGITS_XS;   // Xs/W1T [*][72]  (144 B rows)
 #define HS 40            // Hs/DLs [ROWS][40] (80 B rows)
 #define TS 136           // XT/HT/DLT/DHT [*][136] (272 B rows)
-#define WS 40            // W1T/W2s/W2T [*][40] (80 B rows; K-padded zeros)
-
-typedef __attribute__((ext_vector_type(8))) short bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef unsigned short u16;
-
-__device__ __forceinline__ float bf2f(u16 v) {
-  union { float f; unsigned u; } c;
-  c.u = ((unsigned)v) << 16;
-  return c.f;
-}
-
-__device__ __forceinline__ u16 f2bf(float f) {
-  union { float f; unsigned u; } c;
-  c.f = f;
-  unsigned lsb = (c.u >> 16) & 1u;
-  c.u += 0x7fffu + lsb;        // round-to-nearest-even
-  return (u16)(c.u >> 16);
-}
-
-__device__ __forceinline__ float fast_rcp(float x) {
-  return __builtin_amdgcn_rcpf(x);   // v_rcp_f32, ~1 ulp — no div sequence
-}
+constexpr int WS = DIGITS_WS;   // W2s/W2T [*][40] (80 B rows; K-padded zeros)
 
 // ---------------------------------------------------------------------------
 // standardize
@@ -183,21 +167,11 @@ standardize_apply_kernel(const float* __restrict__ X, long long n_elems, int D,
   }
 }
 
-// ---------------------------------------------------------------------------
-// flat master/grads layout (floats):
-//   [0, 2048)     W1 [IN][HID]
-//   [2048, 2080)  b1 [HID]
-//   [2080, 2592)  W2 [HID][CPAD]  (cols >= CLS stay zero)
-//   [2592, 2608)  b2 [CPAD]
-//   [2608]        loss (grads buffer only)
-// ---------------------------------------------------------------------------
-
-#define OFF_W1 0
-#define OFF_B1 2048
-#define OFF_W2 2080
-#define OFF_B2 2592
-#define OFF_LOSS 2608
-#define NPARAM 2608
+// flat master/grads layout and the per-workgroup slab (tabular_launch.h)
+constexpr int OFF_W1 = DIGITS_OFF_W1, OFF_B1 = DIGITS_OFF_B1;
+constexpr int OFF_W2 = DIGITS_OFF_W2, OFF_B2 = DIGITS_OFF_B2;
+constexpr int NPARAM = DIGITS_NPARAM, OFF_LOSS = NPARAM;
+constexpr int SLAB = DIGITS_SLAB;
 
 // ---------------------------------------------------------------------------
 // dynamic-LDS carve shared by mlp_step / mlp_train_steps
@@ -275,31 +249,13 @@ __device__ __forceinline__ Lds carve(char* smem) {
 // exactly the LDS layout, so the training prologue is one straight
 // vectorized copy instead of a per-element transposed gather. Writers:
 // the Adam phases (in-kernel and adam_step) and the host on
-// init/load_state_dict.
-#define WIMG_W1T 0
-#define WIMG_W2S (HID * XS)
-#define WIMG_W2T (HID * XS + HID * WS)
-#define WIMG_N   (HID * XS + HID * WS + CPAD * WS)
-
+// init/load_state_dict. Offsets: tabular_launch.h DIGITS_WIMG_*; the
+// per-param store: tabular_common.h wimg_write.
 __device__ __forceinline__ void load_weight_images_packed(
     const Lds& L, const u16* __restrict__ wimg) {
   bf16x8* dst = (bf16x8*)&L.W1T[0][0];   // W1T..W2T are contiguous in LDS
   const bf16x8* src = (const bf16x8*)wimg;
-  for (int i = threadIdx.x; i < WIMG_N / 8; i += BLOCK) dst[i] = src[i];
-}
-
-__device__ __forceinline__ void wimg_write(u16* __restrict__ wimg, int i, u16 wb) {
-  if (i < OFF_B1) {                       // W1: i = in*HID + h
-    const int in = i >> 5;                // /HID (32)
-    const int h = i & 31;
-    wimg[WIMG_W1T + h * XS + in] = wb;
-  } else if (i >= OFF_W2 && i < OFF_B2) { // W2: j = h*CPAD + c
-    const int j = i - OFF_W2;
-    const int h = j >> 4;                 // /CPAD (16)
-    const int c = j & 15;
-    wimg[WIMG_W2S + h * WS + c] = wb;
-    wimg[WIMG_W2T + c * WS + h] = wb;
-  }
+  for (int i = threadIdx.x; i < DIGITS_WIMG_N / 8; i += BLOCK) dst[i] = src[i];
 }
 
 // prefetch biases into LDS alongside the other prologue loads — the
@@ -405,35 +361,19 @@ __device__ __forceinline__ void chunk_fwd_bwd(
 
   // ---- fwd2: L^T = W2T @ B(Hs);  D: c = lg*4+r, row = wrow+lr --------------
   {
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    f32x4 acc[1] = {{0.f, 0.f, 0.f, 0.f}};
     const bf16x8 a = *(const bf16x8*)&L.W2T[lr][lg * 8];
     const bf16x8 b = *(const bf16x8*)&L.Hs[wrow + lr][lg * 8];
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc, 0, 0, 0);
+    acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc[0], 0, 0, 0);
 
     const int row = wrow + lr;
     const bool valid = (row0 + row) < Nvalid;
     const int label = valid ? y[row0 + row] : -1;
 
-    float logit[4];
-    float m = -1e30f;
-    #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int c = lg * 4 + r;
-      logit[r] = (c < CLS) ? acc[r] + b2[c] : -1e30f;
-      m = fmaxf(m, logit[r]);
-    }
-    // row max / sum across the 4 lane-groups holding this row's classes
-    m = fmaxf(m, __shfl_xor(m, 16, 64));
-    m = fmaxf(m, __shfl_xor(m, 32, 64));
-    float e[4], s = 0.f;
-    #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int c = lg * 4 + r;
-      e[r] = (c < CLS) ? __expf(logit[r] - m) : 0.f;
-      s += e[r];
-    }
-    s += __shfl_xor(s, 16, 64);
-    s += __shfl_xor(s, 32, 64);
+    float logit[1][4], e[1][4];
+    head_logits<1>(logit, acc, b2, CLS, lg);
+    const float m = head_row_max<1>(logit);
+    const float s = head_exp_sum<1>(e, logit, m, CLS, lg);
     const float rs = fast_rcp(s);
     const float logs = __logf(s);
     float db2_acc[4];
@@ -441,12 +381,12 @@ __device__ __forceinline__ void chunk_fwd_bwd(
     #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int c = lg * 4 + r;
-      const float dl = valid ? (e[r] * rs - (c == label ? 1.f : 0.f)) * invBtot : 0.f;
+      const float dl = valid ? (e[0][r] * rs - (c == label ? 1.f : 0.f)) * invBtot : 0.f;
       const u16 dlb = f2bf(dl);
       L.DLs[row][c] = dlb;
       L.DLT[c][row] = dlb;
       db2_acc[r] = dl;
-      if (valid && c == label) loss_acc = -(logit[r] - m - logs) * invBtot;
+      if (valid && c == label) loss_acc = -(logit[0][r] - m - logs) * invBtot;
     }
     // reduce db2/loss over the 16 row-lanes (lr bits) first, then ONE
     // plain store per (wave, class) into this wave's partial row: the
@@ -488,10 +428,7 @@ __device__ __forceinline__ void chunk_fwd_bwd(
       float dh = hv > 0.f ? acc[r] : 0.f;
       L.DHT[h][row] = f2bf(dh);
       // db1[h]: sum this row-block's contribution across the 16 lr lanes
-      dh += __shfl_xor(dh, 1, 64);
-      dh += __shfl_xor(dh, 2, 64);
-      dh += __shfl_xor(dh, 4, 64);
-      dh += __shfl_xor(dh, 8, 64);
+      dh = row_sum16(dh);
       if (lr == 0) L.part[wave * PART + h] = dh;
     }
   }
@@ -535,7 +472,9 @@ __device__ __forceinline__ void chunk_fwd_bwd(
 }
 
 // ---------------------------------------------------------------------------
-// per-step kernel (multi-workgroup; DP path — grads via global atomics)
+// per-step kernel (multi-workgroup; grads via global atomics). Kept for the
+// kernel tests and benchmarks/probe_steps.py: every training path, DP
+// included, runs mlp_step_fused_kernel below.
 // ---------------------------------------------------------------------------
 
 extern "C" __global__ void __launch_bounds__(BLOCK)
@@ -592,12 +531,10 @@ mlp_step_kernel(const u16* __restrict__ Xbf, const int* __restrict__ y, int B,
 // launch. Each workgroup writes its complete partial-grad slab (plain
 // stores), publishes it with the agent-scope release + ticket-counter
 // hand-off of guide §6 G16 (split-K seam form), and the LAST-arriving
-// workgroup acquires, reduces the slabs and applies Adam. Single-GPU path
-// only (the DP path needs the summed grads for RCCL and keeps
-// mlp_step_kernel + adam_step_kernel).
+// workgroup acquires, reduces the slabs and applies Adam. The DP path needs
+// the summed grads for RCCL: it runs this kernel in reduce-only mode
+// (grads_out) and applies Adam afterwards with adam_step_kernel.
 // ---------------------------------------------------------------------------
-
-#define SLAB 2624   // NPARAM + loss, padded to a 16-float multiple
 
 extern "C" __global__ void __launch_bounds__(BLOCK)
 mlp_step_fused_kernel(const u16* __restrict__ Xbf, const int* __restrict__ y,
@@ -759,8 +696,8 @@ mlp_step_fused_kernel(const u16* __restrict__ Xbf, const int* __restrict__ y,
 #endif
   // ---- every WG reduces its own param stripe + applies Adam ----------------
   const float t_new = (float)(lossu[3] + 1u);
-  const float corr1 = fast_rcp(1.f - __powf(beta1, t_new));
-  const float corr2 = fast_rcp(1.f - __powf(beta2, t_new));
+  float corr1, corr2;
+  adam_bias_corr(beta1, beta2, t_new, corr1, corr2);
   const int span = (NPARAM + 1 + n_wg - 1) / n_wg;
   const int lo = blockIdx.x * span;
   const int hi = min(lo + span, NPARAM + 1);
@@ -789,14 +726,12 @@ mlp_step_fused_kernel(const u16* __restrict__ Xbf, const int* __restrict__ y,
       continue;
     }
     const int j = i - lo;
-    const float p_old = use_pre ? pre[j] : master[i];
-    const float m_old = use_pre ? pre[span_pre + j] : m[i];
-    const float v_old = use_pre ? pre[2 * span_pre + j] : v[i];
-    const float mi = beta1 * m_old + (1.f - beta1) * g;
-    const float vi = beta2 * v_old + (1.f - beta2) * g * g;
+    float p = use_pre ? pre[j] : master[i];
+    float mi = use_pre ? pre[span_pre + j] : m[i];
+    float vi = use_pre ? pre[2 * span_pre + j] : v[i];
+    adam_update(p, mi, vi, g, lr, beta1, beta2, eps, corr1, corr2);
     m[i] = mi;
     v[i] = vi;
-    const float p = p_old - lr * (mi * corr1) * fast_rcp(sqrtf(vi * corr2) + eps);
     master[i] = p;
     const u16 wb = f2bf(p);
     bfmirror[i] = wb;
@@ -821,8 +756,7 @@ adam_step_kernel(float* __restrict__ master, u16* __restrict__ bfmirror,
   __shared__ float corr1, corr2;
   if (threadIdx.x == 0) {
     const int t = ++(*t_dev);
-    corr1 = fast_rcp(1.f - __powf(beta1, (float)t));
-    corr2 = fast_rcp(1.f - __powf(beta2, (float)t));
+    adam_bias_corr(beta1, beta2, (float)t, corr1, corr2);
   }
   __syncthreads();
   // batch 4 strided elements' loads per iteration so the g/m/v/master
@@ -846,12 +780,11 @@ adam_step_kernel(float* __restrict__ master, u16* __restrict__ bfmirror,
     #pragma unroll
     for (int u = 0; u < 4; ++u) {
       if (u < n) {
-        const float mi = beta1 * mi_[u] + (1.f - beta1) * g[u];
-        const float vi = beta2 * vi_[u] + (1.f - beta2) * g[u] * g[u];
+        float p = p_[u], mi = mi_[u], vi = vi_[u];
+        adam_update(p, mi, vi, g[u], lr, beta1, beta2, eps, corr1, corr2);
         const int i = idx[u];
         m[i] = mi;
         v[i] = vi;
-        const float p = p_[u] - lr * (mi * corr1) * fast_rcp(sqrtf(vi * corr2) + eps);
         master[i] = p;
         const u16 wb = f2bf(p);
         bfmirror[i] = wb;
@@ -937,17 +870,12 @@ mlp_train_steps_kernel(const u16* __restrict__ Xbf,  // [N][IN] staged bf16
     // ---- fused in-LDS Adam --------------------------------------------------
     b1t *= beta1;
     b2t *= beta2;
-    const float corr1 = fast_rcp(1.f - b1t);
-    const float corr2 = fast_rcp(1.f - b2t);
+    const float corr1 = adam_corr(b1t);
+    const float corr2 = adam_corr(b2t);
 
-    #define ADAM_UPD(i, g)                                                    \
-      {                                                                       \
-        const float mi = beta1 * m_s[i] + (1.f - beta1) * (g);                \
-        const float vi = beta2 * v_s[i] + (1.f - beta2) * (g) * (g);          \
-        m_s[i] = mi;                                                          \
-        v_s[i] = vi;                                                          \
-        master_s[i] -= lr * (mi * corr1) * fast_rcp(sqrtf(vi * corr2) + eps); \
-      }
+    auto adam_at = [&](int i, float g) {
+      adam_update(master_s[i], m_s[i], v_s[i], g, lr, beta1, beta2, eps, corr1, corr2);
+    };
 
     {
       const int ht = wave & 1, it = wave >> 1;
@@ -956,7 +884,7 @@ mlp_train_steps_kernel(const u16* __restrict__ Xbf,  // [N][IN] staged bf16
         const int h = ht * 16 + lg * 4 + r;
         const int in = it * 16 + ln;
         const int idx = OFF_W1 + in * HID + h;
-        ADAM_UPD(idx, acc.dW1[r]);
+        adam_at(idx, acc.dW1[r]);
         L.W1T[h][in] = f2bf(master_s[idx]);
       }
     }
@@ -965,7 +893,7 @@ mlp_train_steps_kernel(const u16* __restrict__ Xbf,  // [N][IN] staged bf16
       for (int r = 0; r < 4; ++r) {
         const int h = wave * 16 + lg * 4 + r;
         const int idx = OFF_W2 + h * CPAD + ln;
-        ADAM_UPD(idx, acc.dW2[r]);
+        adam_at(idx, acc.dW2[r]);
         const u16 wb = f2bf(master_s[idx]);
         L.W2s[h][ln] = wb;
         L.W2T[ln][h] = wb;
@@ -973,12 +901,11 @@ mlp_train_steps_kernel(const u16* __restrict__ Xbf,  // [N][IN] staged bf16
     }
     if (wave == 2) {
       if (l < HID) {
-        ADAM_UPD(OFF_B1 + l, L.db1[l]);
+        adam_at(OFF_B1 + l, L.db1[l]);
       } else if (l < HID + CPAD) {
-        ADAM_UPD(OFF_B2 + (l - HID), L.db2[l - HID]);
+        adam_at(OFF_B2 + (l - HID), L.db2[l - HID]);
       }
     }
-    #undef ADAM_UPD
     __syncthreads();   // weights updated before next step's fwd
   }
 
@@ -1054,45 +981,26 @@ mlp_predict_kernel(const float* __restrict__ X, int B,
 
   // fwd2: L^T = W2T @ B(Hs); argmax/softmax over the class axis
   {
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    f32x4 acc[1] = {{0.f, 0.f, 0.f, 0.f}};
     const bf16x8 a = *(const bf16x8*)&L.W2T[lr][lg * 8];
     const bf16x8 b = *(const bf16x8*)&L.Hs[wrow + lr][lg * 8];
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc, 0, 0, 0);
+    acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc[0], 0, 0, 0);
 
     const int row = wrow + lr;
-    float best = -1e30f;
-    int bcol = CLS;
-    float logit[4];
-    #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int c = lg * 4 + r;
-      logit[r] = (c < CLS) ? acc[r] + b2[c] : -1e30f;
-      // ties pick the lowest class (match torch.argmax)
-      if (logit[r] > best) { best = logit[r]; bcol = c; }
-    }
-    #pragma unroll
-    for (int d = 16; d < 64; d <<= 1) {
-      const float ov = __shfl_xor(best, d, 64);
-      const int oc = __shfl_xor(bcol, d, 64);
-      if (ov > best || (ov == best && oc < bcol)) { best = ov; bcol = oc; }
-    }
+    float best;
+    int bcol;
+    float logit[1][4];
+    head_logits<1>(logit, acc, b2, CLS, lg);
+    head_argmax<1>(logit, CLS, lg, best, bcol);
     if (lg == 0 && row0 + row < B) preds[row0 + row] = bcol;
     if (probs != nullptr) {
-      float s = 0.f, e[4];
-      #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int c = lg * 4 + r;
-        e[r] = (c < CLS) ? __expf(logit[r] - best) : 0.f;
-        s += e[r];
-      }
-      s += __shfl_xor(s, 16, 64);
-      s += __shfl_xor(s, 32, 64);
-      const float rs = fast_rcp(s);
+      float e[1][4];
+      const float rs = fast_rcp(head_exp_sum<1>(e, logit, best, CLS, lg));
       #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int c = lg * 4 + r;
         if (c < CLS && row0 + row < B) {
-          probs[(row0 + row) * CLS + c] = e[r] * rs;
+          probs[(row0 + row) * CLS + c] = e[0][r] * rs;
         }
       }
     }

@@ -1,47 +1,12 @@
 // Torch bindings for the CDNA4 tabular hot-path kernels
-// (kernels: tabular_kernels.hip). All launches go to the current torch
-// stream so they compose with torch.cuda.graphs capture and RCCL work.
+// (tabular_kernels.hip, tabular_gen.hip; launchers and layout constants:
+// tabular_launch.h). All launches go to the current torch stream so they
+// compose with torch.cuda.graphs capture and RCCL work.
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
-extern "C" {
-void launch_standardize_fit(const float*, long long, int, float*, float*, float,
-                            double*, hipStream_t);
-void launch_standardize_apply(const float*, long long, int, int, const float*,
-                              const float*, unsigned short*, hipStream_t);
-// generalized-geometry kernels (tabular_gen.hip)
-int gen_rt_for_hid(int);
-int launch_mlp_step_gen(const unsigned short*, const int*, int, int, int, int,
-                        int, const unsigned short*, const float*, float*, int,
-                        int, float, hipStream_t);
-void launch_reduce_adam_gen(const float*, int, int, int, int, int, float*,
-                            unsigned short*, float*, float*, int*, float*,
-                            float, float, float, float, unsigned short*, float*,
-                            unsigned*, hipStream_t);
-int launch_mlp_predict_gen(const float*, int, int, int, int, int, const float*,
-                           const float*, const unsigned short*, const float*,
-                           int*, float*, hipStream_t);
-void launch_adam_step_gen(float*, unsigned short*, const float*, float*, float*,
-                          int*, int, int, int, int, float, float, float, float,
-                          unsigned short*, hipStream_t);
-void launch_mlp_step(const unsigned short*, const int*, int, const unsigned short*,
-                     const unsigned short*, const float*, float*, float,
-                     hipStream_t);
-int launch_mlp_train_steps(const unsigned short*, const int*, long long, int, int,
-                           float*, unsigned short*, float*, float*, int*, float*,
-                           float, float, float, float, hipStream_t);
-int launch_mlp_step_fused(const unsigned short*, const int*, int,
-                          const unsigned short*, const unsigned short*, float*,
-                          unsigned short*, float*, float*, int*, float*, unsigned*,
-                          float*, float, float, float, float, float, int, float*,
-                          unsigned short*, hipStream_t);
-void launch_mlp_predict(const float*, int, const float*, const float*,
-                        const unsigned short*, const unsigned short*, const float*,
-                        int*, float*, hipStream_t);
-void launch_adam_step(float*, unsigned short*, const float*, float*, float*, int*,
-                      float, float, float, float, unsigned short*, hipStream_t);
-}
+#include "tabular_launch.h"
 
 namespace {
 
@@ -59,8 +24,55 @@ const unsigned short* bf16_ptr(const torch::Tensor& t) {
   return reinterpret_cast<const unsigned short*>(t.data_ptr());
 }
 
-unsigned short* bf16_mut_ptr(torch::Tensor& t) {
+unsigned short* bf16_mut_ptr(const torch::Tensor& t) {
   return reinterpret_cast<unsigned short*>(t.data_ptr());
+}
+
+// optional tensor -> checked data pointer, or null when absent
+template <typename T>
+T* opt_ptr(const c10::optional<torch::Tensor>& t, torch::ScalarType dtype,
+           const char* name, int64_t min_numel = 0) {
+  if (!t.has_value()) return nullptr;
+  check(*t, dtype, name);
+  TORCH_CHECK(t->numel() >= min_numel, name, " too small: needs ", min_numel,
+              " elements");
+  return reinterpret_cast<T*>(t->data_ptr());
+}
+
+// the specialized kernels' packed weight image has one fixed size
+unsigned short* digits_wimg_ptr(const c10::optional<torch::Tensor>& wimg) {
+  TORCH_CHECK(!wimg.has_value() || wimg->numel() == DIGITS_WIMG_N,
+              "wimg must be the packed ", DIGITS_WIMG_N, "-elem image buffer");
+  return opt_ptr<unsigned short>(wimg, torch::kBFloat16, "wimg");
+}
+
+// Adam state as every optimizer entry point takes it
+struct AdamState {
+  float* master;
+  unsigned short* bfmirror;
+  float* m;
+  float* v;
+  int* t_dev;
+};
+
+AdamState adam_state(const torch::Tensor& master, const torch::Tensor& bfmirror,
+                     const torch::Tensor& m, const torch::Tensor& v,
+                     const torch::Tensor& t_dev, int64_t nparam) {
+  check(master, torch::kFloat32, "master");
+  check(bfmirror, torch::kBFloat16, "bfmirror");
+  check(m, torch::kFloat32, "m");
+  check(v, torch::kFloat32, "v");
+  check(t_dev, torch::kInt32, "t_dev");
+  TORCH_CHECK(master.numel() >= nparam && bfmirror.numel() >= nparam &&
+                  m.numel() >= nparam && v.numel() >= nparam && t_dev.numel() >= 1,
+              "Adam state too small: master/bfmirror/m/v need ", nparam,
+              " elements, t_dev one");
+  return {master.data_ptr<float>(), bf16_mut_ptr(bfmirror), m.data_ptr<float>(),
+          v.data_ptr<float>(), t_dev.data_ptr<int>()};
+}
+
+int gen_nparam(int64_t inp, int64_t hid, int64_t cpad) {
+  return (int)(inp * hid + hid + hid * cpad + cpad);
 }
 
 }  // namespace
@@ -105,9 +117,12 @@ void mlp_step(torch::Tensor Xbf, torch::Tensor y, torch::Tensor W1bf,
   check(W2bf, torch::kBFloat16, "W2bf");
   check(master, torch::kFloat32, "master");
   check(grads, torch::kFloat32, "grads");
-  TORCH_CHECK(Xbf.size(1) == 64, "IN must be 64");
-  TORCH_CHECK(W1bf.numel() == 64 * 32 && W2bf.numel() == 32 * 16, "weight shapes");
-  TORCH_CHECK(grads.numel() >= 2609, "grads must hold 2608 params + loss");
+  TORCH_CHECK(Xbf.size(1) == DIGITS_IN, "IN must be ", DIGITS_IN);
+  TORCH_CHECK(W1bf.numel() == DIGITS_IN * DIGITS_HID &&
+                  W2bf.numel() == DIGITS_HID * DIGITS_CPAD,
+              "weight shapes");
+  TORCH_CHECK(grads.numel() >= DIGITS_NPARAM + 1, "grads must hold ",
+              DIGITS_NPARAM, " params + loss");
   launch_mlp_step(bf16_ptr(Xbf), y.data_ptr<int>(), (int)Xbf.size(0),
                   bf16_ptr(W1bf), bf16_ptr(W2bf), master.data_ptr<float>(),
                   grads.data_ptr<float>(), (float)invBtot, current_stream());
@@ -123,33 +138,21 @@ bool mlp_step_fused(torch::Tensor Xbf, torch::Tensor y, torch::Tensor W1bf,
                     c10::optional<torch::Tensor> wimg = c10::nullopt) {
   check(Xbf, torch::kBFloat16, "Xbf");
   check(y, torch::kInt32, "y");
-  check(master, torch::kFloat32, "master");
-  check(bfmirror, torch::kBFloat16, "bfmirror");
+  const AdamState st = adam_state(master, bfmirror, m, v, t_dev, DIGITS_NPARAM);
   check(slabs, torch::kFloat32, "slabs");
   check(counter, torch::kUInt32, "counter");
   check(loss_out, torch::kFloat32, "loss_out");
-  TORCH_CHECK(Xbf.size(1) == 64, "IN must be 64");
-  TORCH_CHECK(slabs.dim() == 2 && slabs.size(1) == 2624, "slabs must be [n][2624]");
-  float* grads_ptr = nullptr;
-  if (grads_out.has_value()) {
-    check(*grads_out, torch::kFloat32, "grads_out");
-    TORCH_CHECK(grads_out->numel() >= 2609, "grads_out must hold params + loss");
-    grads_ptr = grads_out->data_ptr<float>();
-  }
-  unsigned short* wimg_ptr = nullptr;
-  if (wimg.has_value()) {
-    check(*wimg, torch::kBFloat16, "wimg");
-    TORCH_CHECK(wimg->numel() == 4224, "wimg must be the packed 4224-elem image buffer");
-    wimg_ptr = bf16_mut_ptr(*wimg);
-  }
+  TORCH_CHECK(Xbf.size(1) == DIGITS_IN, "IN must be ", DIGITS_IN);
+  TORCH_CHECK(slabs.dim() == 2 && slabs.size(1) == DIGITS_SLAB, "slabs must be [n][",
+              DIGITS_SLAB, "]");
   const int rc = launch_mlp_step_fused(
       bf16_ptr(Xbf), y.data_ptr<int>(), (int)Xbf.size(0), bf16_ptr(W1bf),
-      bf16_ptr(W2bf), master.data_ptr<float>(), bf16_mut_ptr(bfmirror),
-      m.data_ptr<float>(), v.data_ptr<float>(), t_dev.data_ptr<int>(),
+      bf16_ptr(W2bf), st.master, st.bfmirror, st.m, st.v, st.t_dev,
       slabs.data_ptr<float>(), (unsigned*)counter.data_ptr(),
       loss_out.data_ptr<float>(), (float)invBtot, (float)lr, (float)beta1,
-      (float)beta2, (float)eps, (int)slabs.size(0), grads_ptr, wimg_ptr,
-      current_stream());
+      (float)beta2, (float)eps, (int)slabs.size(0),
+      opt_ptr<float>(grads_out, torch::kFloat32, "grads_out", DIGITS_NPARAM + 1),
+      digits_wimg_ptr(wimg), current_stream());
   TORCH_CHECK(rc != -2, "mlp_step_fused: hipFuncSetAttribute(LDS) failed");
   return rc == 0;
 }
@@ -161,17 +164,12 @@ bool mlp_train_steps(torch::Tensor Xbf, torch::Tensor y, int64_t batch,
                      double eps) {
   check(Xbf, torch::kBFloat16, "Xbf");
   check(y, torch::kInt32, "y");
-  check(master, torch::kFloat32, "master");
-  check(bfmirror, torch::kBFloat16, "bfmirror");
-  check(m, torch::kFloat32, "m");
-  check(v, torch::kFloat32, "v");
-  check(t_dev, torch::kInt32, "t_dev");
+  const AdamState st = adam_state(master, bfmirror, m, v, t_dev, DIGITS_NPARAM);
   check(loss_out, torch::kFloat32, "loss_out");
-  TORCH_CHECK(Xbf.size(1) == 64, "IN must be 64");
+  TORCH_CHECK(Xbf.size(1) == DIGITS_IN, "IN must be ", DIGITS_IN);
   const int rc = launch_mlp_train_steps(
       bf16_ptr(Xbf), y.data_ptr<int>(), Xbf.size(0), (int)batch, (int)n_steps,
-      master.data_ptr<float>(), bf16_mut_ptr(bfmirror), m.data_ptr<float>(),
-      v.data_ptr<float>(), t_dev.data_ptr<int>(), loss_out.data_ptr<float>(),
+      st.master, st.bfmirror, st.m, st.v, st.t_dev, loss_out.data_ptr<float>(),
       (float)lr, (float)beta1, (float)beta2, (float)eps, current_stream());
   TORCH_CHECK(rc != -2, "mlp_train_steps: hipFuncSetAttribute(LDS) failed");
   return rc == 0;   // false -> shape constraints unmet, caller falls back
@@ -182,15 +180,11 @@ void mlp_predict(torch::Tensor X, torch::Tensor mean, torch::Tensor invstd,
                  torch::Tensor preds, c10::optional<torch::Tensor> probs) {
   check(X, torch::kFloat32, "X");
   check(preds, torch::kInt32, "preds");
-  TORCH_CHECK(X.size(1) == 64, "IN must be 64");
-  float* probs_ptr = nullptr;
-  if (probs.has_value()) {
-    check(*probs, torch::kFloat32, "probs");
-    probs_ptr = probs->data_ptr<float>();
-  }
+  TORCH_CHECK(X.size(1) == DIGITS_IN, "IN must be ", DIGITS_IN);
   launch_mlp_predict(X.data_ptr<float>(), (int)X.size(0), mean.data_ptr<float>(),
                      invstd.data_ptr<float>(), bf16_ptr(W1bf), bf16_ptr(W2bf),
-                     master.data_ptr<float>(), preds.data_ptr<int>(), probs_ptr,
+                     master.data_ptr<float>(), preds.data_ptr<int>(),
+                     opt_ptr<float>(probs, torch::kFloat32, "probs"),
                      current_stream());
 }
 
@@ -198,22 +192,11 @@ void adam_step(torch::Tensor master, torch::Tensor bfmirror, torch::Tensor grads
                torch::Tensor m, torch::Tensor v, torch::Tensor t_dev, double lr,
                double beta1, double beta2, double eps,
                c10::optional<torch::Tensor> wimg = c10::nullopt) {
-  check(master, torch::kFloat32, "master");
-  check(bfmirror, torch::kBFloat16, "bfmirror");
+  const AdamState st = adam_state(master, bfmirror, m, v, t_dev, DIGITS_NPARAM);
   check(grads, torch::kFloat32, "grads");
-  check(m, torch::kFloat32, "m");
-  check(v, torch::kFloat32, "v");
-  check(t_dev, torch::kInt32, "t_dev");
-  unsigned short* wimg_ptr = nullptr;
-  if (wimg.has_value()) {
-    check(*wimg, torch::kBFloat16, "wimg");
-    TORCH_CHECK(wimg->numel() == 4224, "wimg must be the packed 4224-elem image buffer");
-    wimg_ptr = bf16_mut_ptr(*wimg);
-  }
-  launch_adam_step(master.data_ptr<float>(), bf16_mut_ptr(bfmirror),
-                   grads.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(),
-                   t_dev.data_ptr<int>(), (float)lr, (float)beta1, (float)beta2,
-                   (float)eps, wimg_ptr, current_stream());
+  launch_adam_step(st.master, st.bfmirror, grads.data_ptr<float>(), st.m, st.v,
+                   st.t_dev, (float)lr, (float)beta1, (float)beta2, (float)eps,
+                   digits_wimg_ptr(wimg), current_stream());
 }
 
 // ---------------------------------------------------------------------------
@@ -230,7 +213,7 @@ bool mlp_step_gen(torch::Tensor Xbf, torch::Tensor y, int64_t hid, int64_t cls,
   check(slabs, torch::kFloat32, "slabs");
   const int inp = (int)Xbf.size(1);
   const int cpad = cls <= 16 ? 16 : 32;
-  const int nparam = (int)(inp * hid + hid + hid * cpad + cpad);
+  const int nparam = gen_nparam(inp, hid, cpad);
   TORCH_CHECK(inp % 32 == 0, "staged input width must be a multiple of 32");
   TORCH_CHECK(master.numel() >= nparam, "master too small for geometry");
   TORCH_CHECK(wimg.numel() >= (int64_t)hid * inp + hid * 32 + cpad * hid,
@@ -257,32 +240,19 @@ void reduce_adam_gen(torch::Tensor slabs, int64_t n_wg, int64_t inp, int64_t hid
                      c10::optional<torch::Tensor> grads_out = c10::nullopt) {
   check(counter, torch::kUInt32, "counter");
   check(slabs, torch::kFloat32, "slabs");
-  check(master, torch::kFloat32, "master");
-  check(bfmirror, torch::kBFloat16, "bfmirror");
   check(loss_out, torch::kFloat32, "loss_out");
   TORCH_CHECK(cpad == 16 || cpad == 32, "cpad must be 16 or 32");
-  const int nparam = (int)(inp * hid + hid + hid * cpad + cpad);
+  const int nparam = gen_nparam(inp, hid, cpad);
+  const AdamState st = adam_state(master, bfmirror, m, v, t_dev, nparam);
   TORCH_CHECK(slabs.dim() == 2 && slabs.size(1) >= nparam + 2, "slab stride");
   TORCH_CHECK(n_wg >= 1 && n_wg <= slabs.size(0), "n_wg out of range");
-  unsigned short* wimg_ptr = nullptr;
-  if (wimg.has_value()) {
-    check(*wimg, torch::kBFloat16, "wimg");
-    wimg_ptr = bf16_mut_ptr(*wimg);
-  }
-  float* grads_ptr = nullptr;
-  if (grads_out.has_value()) {
-    check(*grads_out, torch::kFloat32, "grads_out");
-    TORCH_CHECK(grads_out->numel() >= nparam + 1, "grads_out too small");
-    grads_ptr = grads_out->data_ptr<float>();
-  }
-  launch_reduce_adam_gen(slabs.data_ptr<float>(), (int)n_wg,
-                         (int)slabs.size(1), (int)inp, (int)hid, (int)cpad,
-                         master.data_ptr<float>(), bf16_mut_ptr(bfmirror),
-                         m.data_ptr<float>(), v.data_ptr<float>(),
-                         t_dev.data_ptr<int>(), loss_out.data_ptr<float>(),
-                         (float)lr, (float)beta1, (float)beta2, (float)eps,
-                         wimg_ptr, grads_ptr, (unsigned*)counter.data_ptr(),
-                         current_stream());
+  launch_reduce_adam_gen(
+      slabs.data_ptr<float>(), (int)n_wg, (int)slabs.size(1), (int)inp, (int)hid,
+      (int)cpad, st.master, st.bfmirror, st.m, st.v, st.t_dev,
+      loss_out.data_ptr<float>(), (float)lr, (float)beta1, (float)beta2,
+      (float)eps, opt_ptr<unsigned short>(wimg, torch::kBFloat16, "wimg"),
+      opt_ptr<float>(grads_out, torch::kFloat32, "grads_out", nparam + 1),
+      (unsigned*)counter.data_ptr(), current_stream());
 }
 
 void mlp_predict_gen(torch::Tensor X, int64_t inp, int64_t hid, int64_t cls,
@@ -295,16 +265,11 @@ void mlp_predict_gen(torch::Tensor X, int64_t inp, int64_t hid, int64_t cls,
   check(preds, torch::kInt32, "preds");
   TORCH_CHECK(mean.numel() == X.size(1) && invstd.numel() == X.size(1),
               "mean/invstd must match raw feature width");
-  float* probs_ptr = nullptr;
-  if (probs.has_value()) {
-    check(*probs, torch::kFloat32, "probs");
-    probs_ptr = probs->data_ptr<float>();
-  }
   const int rc = launch_mlp_predict_gen(
       X.data_ptr<float>(), (int)X.size(0), (int)X.size(1), (int)inp, (int)hid,
       (int)cls, mean.data_ptr<float>(), invstd.data_ptr<float>(), bf16_ptr(wimg),
-      master.data_ptr<float>(), preds.data_ptr<int>(), probs_ptr,
-      current_stream());
+      master.data_ptr<float>(), preds.data_ptr<int>(),
+      opt_ptr<float>(probs, torch::kFloat32, "probs"), current_stream());
   TORCH_CHECK(rc == 0, "mlp_predict_gen: unsupported geometry or LDS failure");
 }
 
@@ -313,25 +278,23 @@ void adam_step_gen(torch::Tensor master, torch::Tensor bfmirror,
                    torch::Tensor t_dev, int64_t inp, int64_t hid, int64_t cpad,
                    double lr, double beta1, double beta2, double eps,
                    c10::optional<torch::Tensor> wimg = c10::nullopt) {
-  check(master, torch::kFloat32, "master");
-  check(bfmirror, torch::kBFloat16, "bfmirror");
   check(grads, torch::kFloat32, "grads");
   TORCH_CHECK(cpad == 16 || cpad == 32, "cpad must be 16 or 32");
-  const int nparam = (int)(inp * hid + hid + hid * cpad + cpad);
-  TORCH_CHECK(master.numel() >= nparam, "master too small for geometry");
-  unsigned short* wimg_ptr = nullptr;
-  if (wimg.has_value()) {
-    check(*wimg, torch::kBFloat16, "wimg");
-    wimg_ptr = bf16_mut_ptr(*wimg);
-  }
-  launch_adam_step_gen(master.data_ptr<float>(), bf16_mut_ptr(bfmirror),
-                       grads.data_ptr<float>(), m.data_ptr<float>(),
-                       v.data_ptr<float>(), t_dev.data_ptr<int>(), nparam,
-                       (int)inp, (int)hid, (int)cpad, (float)lr, (float)beta1,
-                       (float)beta2, (float)eps, wimg_ptr, current_stream());
+  const int nparam = gen_nparam(inp, hid, cpad);
+  const AdamState st = adam_state(master, bfmirror, m, v, t_dev, nparam);
+  launch_adam_step_gen(st.master, st.bfmirror, grads.data_ptr<float>(), st.m,
+                       st.v, st.t_dev, nparam, (int)inp, (int)hid, (int)cpad,
+                       (float)lr, (float)beta1, (float)beta2, (float)eps,
+                       opt_ptr<unsigned short>(wimg, torch::kBFloat16, "wimg"),
+                       current_stream());
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  // specialized (digits) layout numbers the host side stages buffers with
+  m.attr("WIMG_N") = DIGITS_WIMG_N;   // packed weight image, bf16 elements
+  m.attr("SLAB") = DIGITS_SLAB;       // gradient slab stride, floats
+  m.attr("XS") = DIGITS_XS;           // image row stride of W1T
+  m.attr("WS") = DIGITS_WS;           // image row stride of W2s / W2T
   m.def("standardize_fit", &standardize_fit, "column mean/invstd (CDNA4)");
   m.def("standardize_apply", &standardize_apply, "(x-mean)*invstd -> bf16 (CDNA4)");
   m.def("mlp_step", &mlp_step, "fused MLP fwd+bwd step (CDNA4 MFMA)");
@@ -351,8 +314,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("master"), py::arg("bfmirror"), py::arg("grads"), py::arg("m"),
         py::arg("v"), py::arg("t_dev"), py::arg("lr"), py::arg("beta1"),
         py::arg("beta2"), py::arg("eps"), py::arg("wimg") = c10::nullopt);
-  m.def("gen_rt_for_hid", &gen_rt_for_hid,
-        "rows-per-workgroup for a supported hidden width (0 = unsupported)");
   m.def("mlp_step_gen", &mlp_step_gen,
         "generalized fused step: any (in,hid,cls) geometry; double-buffered "
         "K-tiled MFMA fwd+bwd producing per-WG gradient slabs",

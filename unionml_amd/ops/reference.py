@@ -97,11 +97,7 @@ def standardize_apply(X: torch.Tensor, mean: torch.Tensor, invstd: torch.Tensor)
 
 
 def unpack_master(master: torch.Tensor):
-    W1 = master[OFF_W1 : OFF_W1 + IN * HID].view(IN, HID)
-    b1 = master[OFF_B1 : OFF_B1 + HID]
-    W2 = master[OFF_W2 : OFF_W2 + HID * CPAD].view(HID, CPAD)
-    b2 = master[OFF_B2 : OFF_B2 + CPAD]
-    return W1, b1, W2, b2
+    return unpack_master_g(DIGITS, master)
 
 
 def mlp_step(
@@ -116,6 +112,7 @@ def mlp_step(
     """Fused fwd+bwd reference: accumulates grads (+loss at [NPARAM])
     into ``grads`` exactly like the kernel (which atomically adds onto a
     pre-zeroed buffer)."""
+    # NOT mlp_step_g(DIGITS, ...): this oracle feeds the unrounded hidden activations to layer 2
     _, b1, _, b2 = unpack_master(master)
     X = Xbf.float()
     W1 = W1bf.float()
@@ -163,15 +160,7 @@ def mlp_predict(
     master: torch.Tensor,
     return_probs: bool = False,
 ):
-    _, b1, _, b2 = unpack_master(master)
-    Xs = ((X - mean) * invstd).bfloat16().float()
-    H = torch.relu(Xs @ W1bf.float() + b1)
-    logits = H.bfloat16().float() @ W2bf.float() + b2
-    logits = logits[:, :CLS]
-    preds = logits.argmax(dim=1).int()
-    if return_probs:
-        return preds, torch.softmax(logits, dim=1)
-    return preds
+    return mlp_predict_g(DIGITS, X, mean, invstd, W1bf, W2bf, master, return_probs)
 
 
 # ---------------------------------------------------------------------------
@@ -296,10 +285,4 @@ def adam_step(
     beta2: float = 0.999,
     eps: float = 1e-8,
 ) -> None:
-    g = grads[:NPARAM]
-    m.mul_(beta1).add_(g, alpha=1 - beta1)
-    v.mul_(beta2).addcmul_(g, g, value=1 - beta2)
-    corr1 = 1.0 / (1.0 - beta1**t)
-    corr2 = 1.0 / (1.0 - beta2**t)
-    master[:NPARAM] -= lr * (m * corr1) / (torch.sqrt(v * corr2) + eps)
-    bfmirror[:NPARAM] = master[:NPARAM].bfloat16()
+    adam_step_g(DIGITS, master, bfmirror, grads, m, v, t, lr, beta1, beta2, eps)

@@ -98,10 +98,10 @@ class TabularMLP:
         )
         self._build_wimg()
 
-    _XS, _WS = 72, 40  # specialized-kernel LDS row strides (tabular_kernels.hip)
-
     def _wimg_len(self) -> int:
-        return 4224 if self.use_spec else self.g.wimg_n
+        # the specialized layout's numbers come from the extension
+        # (tabular_launch.h); the image exists only when it is loaded
+        return hip_ext().WIMG_N if self.use_spec else self.g.wimg_n
 
     #: per hidden width: (default rows/WG, small-batch rows/WG). The
     #: small variant keeps >= ~16 workgroups in flight at modest batch
@@ -130,8 +130,9 @@ class TabularMLP:
         g = self.g
         W1, _, W2, _ = ref.unpack_master_g(g, self.master.detach().cpu())
         if self.use_spec:
-            XS, WS = self._XS, self._WS
-            img = torch.zeros(4224, dtype=torch.bfloat16)
+            ext = hip_ext()
+            XS, WS = ext.XS, ext.WS
+            img = torch.zeros(ext.WIMG_N, dtype=torch.bfloat16)
             img[: HID * XS].view(HID, XS)[:, :IN] = W1.t().bfloat16()      # W1T[h][k]
             img[HID * XS : HID * XS + HID * WS].view(HID, WS)[:, :CPAD] = W2.bfloat16()
             img[HID * XS + HID * WS :].view(CPAD, WS)[:, :HID] = W2.t().bfloat16()
@@ -195,22 +196,25 @@ class TabularMLP:
 
     # -- training --------------------------------------------------------------
 
-    def _step_reduce(self, Xbf: torch.Tensor, y: torch.Tensor, invBtot: float, lr: float):
-        """Fused fwd/bwd + in-kernel slab reduction writing the summed
-        grads into self.grads (reduce-only mode: the DP pre-collective
-        kernel — no Adam)."""
+    def _launch_step(self, Xbf, y, invBtot, lr, loss_out, grads_out=None):
+        """One step's launches: a single fused launch for the specialized
+        shape; for generalized shapes the slab-producing step kernel
+        followed by the wide-grid reduce+Adam kernel (the kernel
+        boundary is the inter-WG barrier — full-chip bandwidth for the
+        large-nparam reduction instead of a handshake inside a tiny
+        grid). With ``grads_out`` the launches stop after the slab
+        reduction and write the summed grads (+loss) there: no Adam."""
         g = self.g
         rpw = self._rows_per_wg(Xbf.shape[0])
         n_wg = (Xbf.shape[0] + rpw - 1) // rpw
         self._ensure_slabs(n_wg)
-        loss_out = self.grads[g.nparam : g.nparam + 1]
         ext = hip_ext()
         if self.use_spec:
             ok = ext.mlp_step_fused(
                 Xbf, y, self.W1bf, self.W2bf, self.master, self.bfmirror,
                 self.m, self.v, self.t_dev, self.slabs, self.counter, loss_out,
                 invBtot, lr, ADAM_BETA1, ADAM_BETA2, ADAM_EPS,
-                grads_out=self.grads, wimg=self.wimg,
+                grads_out=grads_out, wimg=self.wimg,
             )
             assert ok, "fused step slab capacity exceeded"
         else:
@@ -223,8 +227,14 @@ class TabularMLP:
                 self.slabs, n_wg, g.inp, g.hid, g.cpad, self.master,
                 self.bfmirror, self.m, self.v, self.t_dev, self.counter,
                 loss_out, lr, ADAM_BETA1, ADAM_BETA2, ADAM_EPS,
-                wimg=self.wimg, grads_out=self.grads,
+                wimg=self.wimg, grads_out=grads_out,
             )
+
+    def _step_reduce(self, Xbf: torch.Tensor, y: torch.Tensor, invBtot: float, lr: float):
+        """Reduce-only step: summed grads (+loss) into self.grads — the
+        DP pre-collective kernel, no Adam."""
+        g = self.g
+        self._launch_step(Xbf, y, invBtot, lr, self.grads[g.nparam : g.nparam + 1], self.grads)
 
     def _adam(self, lr: float):
         g = self.g
@@ -264,35 +274,36 @@ class TabularMLP:
         return self.grads[g.nparam]
 
     def _fused_adam_step(self, Xbf, y, invBtot, lr, loss_out):
-        """One optimizer step: a single fused launch for the specialized
-        shape; for generalized shapes the slab-producing step kernel
-        followed by the wide-grid reduce+Adam kernel (the kernel
-        boundary is the inter-WG barrier — full-chip bandwidth for the
-        large-nparam reduction instead of a handshake inside a tiny
-        grid)."""
-        g = self.g
-        ext = hip_ext()
-        if self.use_spec:
-            ok = ext.mlp_step_fused(
-                Xbf, y, self.W1bf, self.W2bf, self.master, self.bfmirror,
-                self.m, self.v, self.t_dev, self.slabs, self.counter, loss_out,
-                invBtot, lr, ADAM_BETA1, ADAM_BETA2, ADAM_EPS, wimg=self.wimg,
-            )
-            assert ok, "fused step slab capacity exceeded"
+        """One optimizer step (fwd/bwd + slab reduction + Adam), the
+        last loss into ``loss_out``."""
+        self._launch_step(Xbf, y, invBtot, lr, loss_out)
+
+    def _run_epochs(self, run_epoch, epochs: int, key, use_graph: bool) -> float:
+        """Device epoch driver: one eager warmup epoch (also warms the
+        RCCL communicator / memory pool), then capture one epoch into a
+        hipGraph once per ``key`` (capture records without executing)
+        and replay the remaining epochs — or step them eagerly when
+        ``use_graph`` is off or capture fails. Returns the last loss,
+        which both step flavours leave in grads[nparam]."""
+        run_epoch()
+        remaining = epochs - 1
+        if use_graph and self._graph_key != key:
+            try:
+                gph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(gph):
+                    run_epoch()
+                self._graph, self._graph_key = gph, key
+            except RuntimeError as exc:  # e.g. RCCL capture unsupported
+                logger.warning("hipGraph capture failed (%s); eager stepping", exc)
+                self._graph, self._graph_key = None, None
+        if use_graph and self._graph is not None:
+            for _ in range(remaining):
+                self._graph.replay()
         else:
-            rpw = self._rows_per_wg(Xbf.shape[0])
-            n_wg = (Xbf.shape[0] + rpw - 1) // rpw
-            self._ensure_slabs(n_wg)
-            ok = ext.mlp_step_gen(
-                Xbf, y, g.hid, g.classes, rpw, self.wimg, self.master,
-                self.slabs, invBtot,
-            )
-            assert ok, "fused step slab capacity exceeded"
-            ext.reduce_adam_gen(
-                self.slabs, n_wg, g.inp, g.hid, g.cpad, self.master,
-                self.bfmirror, self.m, self.v, self.t_dev, self.counter,
-                loss_out, lr, ADAM_BETA1, ADAM_BETA2, ADAM_EPS, wimg=self.wimg,
-            )
+            for _ in range(remaining):
+                run_epoch()
+        torch.cuda.synchronize(self.device)
+        return float(self.grads[self.g.nparam].item())
 
     def _train_epochs_fused(self, Xbf, y, batches, *, epochs, lr, use_graph) -> float:
         g = self.g
@@ -310,26 +321,8 @@ class TabularMLP:
                     Xbf[off : off + bs], y[off : off + bs], 1.0 / bs, lr, loss_out
                 )
 
-        run_epoch()   # warmup epoch (eager)
-        remaining = epochs - 1
         key = ("fused", len(batches), lr, Xbf.data_ptr(), y.data_ptr())
-        if use_graph and self._graph_key != key:
-            try:
-                gph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(gph):
-                    run_epoch()
-                self._graph, self._graph_key = gph, key
-            except RuntimeError as exc:
-                logger.warning("hipGraph capture failed (%s); eager stepping", exc)
-                self._graph, self._graph_key = None, None
-        if use_graph and self._graph is not None:
-            for _ in range(remaining):
-                self._graph.replay()
-        else:
-            for _ in range(remaining):
-                run_epoch()
-        torch.cuda.synchronize(self.device)
-        return float(loss_out.item())
+        return self._run_epochs(run_epoch, epochs, key, use_graph)
 
     def train_epochs(
         self,
@@ -403,29 +396,8 @@ class TabularMLP:
             # with allreduce the stored loss is already the global mean
             return float(loss.item()) if loss is not None else float("nan")
 
-        # hipGraph path: one eager warmup epoch (also warms the RCCL
-        # communicator / memory pool), then capture one epoch (capture
-        # records without executing) and replay the remaining epochs.
-        run_epoch()
-        remaining = epochs - 1
         key = (n, batch_size, world_size, lr, Xbf.data_ptr(), y.data_ptr())
-        if self._graph_key != key:
-            try:
-                gph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(gph):
-                    run_epoch()
-                self._graph, self._graph_key = gph, key
-            except RuntimeError as exc:  # e.g. RCCL capture unsupported
-                logger.warning("hipGraph capture failed (%s); eager stepping", exc)
-                self._graph, self._graph_key = None, None
-        if self._graph is not None:
-            for _ in range(remaining):
-                self._graph.replay()
-        else:
-            for _ in range(remaining):
-                run_epoch()
-        torch.cuda.synchronize(self.device)
-        return float(self.grads[g.nparam].item())
+        return self._run_epochs(run_epoch, epochs, key, use_graph=True)
 
     # -- inference -------------------------------------------------------------
 
