@@ -32,13 +32,74 @@ __device__ __forceinline__ float fast_rcp(float x) {
   return __builtin_amdgcn_rcpf(x);   // v_rcp_f32, ~1 ulp — no div sequence
 }
 
-// sum over the 16 lanes that share l>>4 (the row axis of an MFMA D tile)
+// x as seen from the lane a DPP control selects within this lane's row of
+// 16. Every lane of the row must be active.
+template <int CTRL>
+__device__ __forceinline__ float dpp_row_f32(float x) {
+  return __int_as_float(__builtin_amdgcn_update_dpp(
+      0, __float_as_int(x), CTRL, 0xF, 0xF, true));
+}
+
+// sum over the 16 lanes that share l>>4 (the row axis of an MFMA D tile),
+// every lane receiving the sum. Four DPP row operations (v_add_f32_dpp):
+// nothing goes through the LDS crossbar, which the ds_bpermute behind
+// __shfl_xor does.
+//
+// Bit for bit the xor-1/2/4/8 __shfl_xor butterfly: the quad_perm stages
+// ARE xor 1 and xor 2. After them every lane of a quad holds the identical
+// sum (IEEE add is commutative, so both partners of a pair compute the
+// same number). Hence lane l^7 holds what lane l^4 holds, and
+// row_half_mirror (lane l reads lane l^7) adds the same two numbers the
+// xor-4 stage added; after it every lane of a half row agrees, lane l^15
+// holds what lane l^8 holds, and row_mirror (l reads l^15) is the xor-8
+// stage. Same pairing tree, same rounding.
 __device__ __forceinline__ float row_sum16(float x) {
-  x += __shfl_xor(x, 1, 64);
-  x += __shfl_xor(x, 2, 64);
-  x += __shfl_xor(x, 4, 64);
-  x += __shfl_xor(x, 8, 64);
+  x += dpp_row_f32<0xB1>(x);    // quad_perm [1,0,3,2]  == xor 1
+  x += dpp_row_f32<0x4E>(x);    // quad_perm [2,3,0,1]  == xor 2
+  x += dpp_row_f32<0x141>(x);   // row_half_mirror      ~  xor 4
+  x += dpp_row_f32<0x140>(x);   // row_mirror           ~  xor 8
   return x;
+}
+
+// The two operands of a fold across lanes l and l ^ D, D = 16 or 32 (the
+// lane-group axis of an MFMA D tile), without the LDS crossbar:
+// v_permlane16_swap exchanges the odd rows of its first operand with the
+// even rows of its second, v_permlane32_swap the upper half of the first
+// with the lower half of the second. With x in both, the first comes back
+// holding the lower partner's x on both lanes and the second the upper
+// partner's. The same two numbers meet as in x op __shfl_xor(x, D), and the
+// folds built on this are commutative, so no bit changes. Every lane must
+// be active. (Measured against ds_bpermute in the fused step:
+// profiles/r03_fused_chain.md.)
+template <int D>
+__device__ __forceinline__ void group_pair(float x, float& a, float& b) {
+  static_assert(D == 16 || D == 32, "row-of-16 or half-wave exchange");
+  const int xi = __float_as_int(x);
+  if constexpr (D == 16) {
+    const auto r = __builtin_amdgcn_permlane16_swap(xi, xi, false, false);
+    a = __int_as_float(r[0]);
+    b = __int_as_float(r[1]);
+  } else {
+    const auto r = __builtin_amdgcn_permlane32_swap(xi, xi, false, false);
+    a = __int_as_float(r[0]);
+    b = __int_as_float(r[1]);
+  }
+}
+
+// x + (x of lane l ^ D), every lane receiving the result
+template <int D>
+__device__ __forceinline__ float group_sum(float x) {
+  float a, b;
+  group_pair<D>(x, a, b);
+  return a + b;
+}
+
+// max(x, x of lane l ^ D)
+template <int D>
+__device__ __forceinline__ float group_max(float x) {
+  float a, b;
+  group_pair<D>(x, a, b);
+  return fmaxf(a, b);
 }
 
 // ---------------------------------------------------------------------------
@@ -146,8 +207,8 @@ __device__ __forceinline__ float head_row_max(const float (&logit)[NCT][4]) {
     #pragma unroll
     for (int r = 0; r < 4; ++r) mx = fmaxf(mx, logit[ct][r]);
   }
-  mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-  mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+  mx = group_max<16>(mx);
+  mx = group_max<32>(mx);
   return mx;
 }
 
@@ -166,8 +227,8 @@ __device__ __forceinline__ float head_exp_sum(float (&e)[NCT][4],
       s += e[ct][r];
     }
   }
-  s += __shfl_xor(s, 16, 64);
-  s += __shfl_xor(s, 32, 64);
+  s = group_sum<16>(s);
+  s = group_sum<32>(s);
   return s;
 }
 

@@ -406,15 +406,13 @@ mlp_step_gen_kernel(const u16* __restrict__ Xbf,   // [N][inp] staged bf16 (zero
         if (valid && c == label) loss_acc = -(logit[ct][r] - mx - logs) * invBtot;
       }
     }
+    // in-row sums first (DPP, every lane active), predicated atomics after
     #pragma unroll
-    for (int bit = 1; bit < 16; bit <<= 1) {
+    for (int ct = 0; ct < G::NCT; ++ct) {
       #pragma unroll
-      for (int ct = 0; ct < G::NCT; ++ct) {
-        #pragma unroll
-        for (int r = 0; r < 4; ++r) db2_acc[ct][r] += __shfl_xor(db2_acc[ct][r], bit, 64);
-      }
-      loss_acc += __shfl_xor(loss_acc, bit, 64);
+      for (int r = 0; r < 4; ++r) db2_acc[ct][r] = row_sum16(db2_acc[ct][r]);
     }
+    loss_acc = row_sum16(loss_acc);
     if (lr_ == 0) {
       #pragma unroll
       for (int ct = 0; ct < G::NCT; ++ct) {
@@ -424,8 +422,8 @@ mlp_step_gen_kernel(const u16* __restrict__ Xbf,   // [N][inp] staged bf16 (zero
         }
       }
     }
-    loss_acc += __shfl_xor(loss_acc, 16, 64);
-    loss_acc += __shfl_xor(loss_acc, 32, 64);
+    loss_acc = group_sum<16>(loss_acc);
+    loss_acc = group_sum<32>(loss_acc);
     if (l == 0) atomicAdd(L.loss, loss_acc);
   }
   __syncthreads();
@@ -441,15 +439,19 @@ mlp_step_gen_kernel(const u16* __restrict__ Xbf,   // [N][inp] staged bf16 (zero
       const bf16x8 a = *(const bf16x8*)&L.W2s[mt * 16 + lr_][lg * 8];
       const bf16x8 b = *(const bf16x8*)&L.DLs[rt * 16 + lr_][lg * 8];
       acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc, 0, 0, 0);
+      float db1_acc[4];
       #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int h = mt * 16 + lg * 4 + r;
         const int row = rt * 16 + lr_;
         const float hv = bf2f(L.HT[h][row]);
-        float dh = hv > 0.f ? acc[r] : 0.f;
+        const float dh = hv > 0.f ? acc[r] : 0.f;
         L.DHT[h][row] = f2bf(dh);
-        dh = row_sum16(dh);
-        if (lr_ == 0) atomicAdd(&L.db1[h], dh);
+        db1_acc[r] = row_sum16(dh);
+      }
+      if (lr_ == 0) {
+        #pragma unroll
+        for (int r = 0; r < 4; ++r) atomicAdd(&L.db1[mt * 16 + lg * 4 + r], db1_acc[r]);
       }
     }
   }

@@ -251,22 +251,54 @@ __device__ __forceinline__ Lds carve(char* smem) {
 // the Adam phases (in-kernel and adam_step) and the host on
 // init/load_state_dict. Offsets: tabular_launch.h DIGITS_WIMG_*; the
 // per-param store: tabular_common.h wimg_write.
-__device__ __forceinline__ void load_weight_images_packed(
-    const Lds& L, const u16* __restrict__ wimg) {
-  bf16x8* dst = (bf16x8*)&L.W1T[0][0];   // W1T..W2T are contiguous in LDS
+//
+// Two-phase form: a load loop compiles to load -> wait -> LDS store per
+// trip, one cold global round trip each. issue_* puts every vector of this
+// thread in flight and returns registers; store_* writes them to LDS after
+// the caller has issued ALL its prologue loads, so the prologue waits once.
+constexpr int WIMG_VECS = DIGITS_WIMG_N / 8;    // 528 vectors over 512 threads
+constexpr int WIMG_TAIL = WIMG_VECS - BLOCK;    // second vector: threads 0..15
+static_assert(WIMG_TAIL > 0 && WIMG_TAIL <= BLOCK, "two vectors per thread at most");
+
+struct WimgRegs {
+  bf16x8 v0, v1;
+};
+
+__device__ __forceinline__ void issue_weight_images_packed(
+    WimgRegs& R, const u16* __restrict__ wimg) {
   const bf16x8* src = (const bf16x8*)wimg;
-  for (int i = threadIdx.x; i < DIGITS_WIMG_N / 8; i += BLOCK) dst[i] = src[i];
+  const int tid = threadIdx.x;
+  R.v0 = src[tid];
+  // unconditional (threads past the tail re-read their first vector and
+  // drop it): a load under a branch made the compiler wait on the spot
+  R.v1 = src[tid < WIMG_TAIL ? BLOCK + tid : tid];
+}
+
+__device__ __forceinline__ void store_weight_images_packed(const WimgRegs& R,
+                                                           const Lds& L) {
+  bf16x8* dst = (bf16x8*)&L.W1T[0][0];   // W1T..W2T are contiguous in LDS
+  const int tid = threadIdx.x;
+  dst[tid] = R.v0;
+  if (tid < WIMG_TAIL) dst[BLOCK + tid] = R.v1;
 }
 
 // prefetch biases into LDS alongside the other prologue loads — the
 // previous launch's agent-scope acquire left L2 cold, so a lazy mid-GEMM
-// b1/b2 read would serialize a full HBM round trip into the fwd chain
-__device__ __forceinline__ void load_biases(const Lds& L,
-                                            const float* __restrict__ b1,
-                                            const float* __restrict__ b2) {
+// b1/b2 read would serialize a full HBM round trip into the fwd chain.
+// Two-phase as well: this thread's bias element travels in a register
+// until the prologue's single wait.
+__device__ __forceinline__ float issue_biases(const float* __restrict__ b1,
+                                              const float* __restrict__ b2) {
   const int tid = threadIdx.x;
-  if (tid < HID) L.b1s[tid] = b1[tid];
-  else if (tid < HID + CPAD) L.b2s[tid - HID] = b2[tid - HID];
+  // unconditional: threads without a bias element re-read b1[0], unused
+  const float* p = tid < HID ? b1 + tid : tid < HID + CPAD ? b2 + (tid - HID) : b1;
+  return *p;
+}
+
+__device__ __forceinline__ void store_biases(float b, const Lds& L) {
+  const int tid = threadIdx.x;
+  if (tid < HID) L.b1s[tid] = b;
+  else if (tid < HID + CPAD) L.b2s[tid - HID] = b;
 }
 
 // fill weight images (W1T/W2s/W2T incl. zero K-pads) from bf16 weight arrays
@@ -288,19 +320,66 @@ __device__ __forceinline__ void load_weight_images(const Lds& L,
   }
 }
 
-// cooperative X-chunk load: Xs row-major + XT transposed, zero batch tail
-__device__ __forceinline__ void load_x_chunk(const u16* __restrict__ Xbf,
-                                             const Lds& L, long long row0,
-                                             long long Nvalid) {
-  for (int i = threadIdx.x; i < ROWS * (IN / 8); i += BLOCK) {
+// cooperative X-chunk load, two-phase like the packed images: thread t
+// owns vector t and t + BLOCK of the chunk's ROWS x IN/8 vectors, plus the
+// label of the row chunk_fwd_bwd gives it (wave*16 + lane%16; the four
+// lane groups of a wave load the same value).
+//
+// Batch tail: a row at or beyond Nvalid loads from row Nvalid-1 instead
+// (always in range: every caller has Nvalid >= 1) and the value is
+// replaced after the wait, by zeros for X and by -1 for the label.
+// Nothing at or beyond Nvalid is read. The loads are unconditional on
+// purpose: a load under `if (row < Nvalid)` merged with a zero default
+// made the compiler wait for it on the spot, one exposed round trip.
+constexpr int X_VECS = ROWS * (IN / 8) / BLOCK;
+static_assert(X_VECS * BLOCK == ROWS * (IN / 8), "whole vectors per thread");
+
+struct XChunkRegs {
+  bf16x8 v[X_VECS];
+  bool vvalid[X_VECS];
+  int label;    // as loaded; chunk_label() applies the tail rule
+  bool valid;   // this thread's softmax row is a real batch row
+};
+
+__device__ __forceinline__ void issue_label(XChunkRegs& R,
+                                            const int* __restrict__ y,
+                                            long long row0, long long Nvalid) {
+  const int tid = threadIdx.x;
+  const long long row = row0 + (tid >> 6) * 16 + (tid & 15);
+  R.valid = row < Nvalid;
+  R.label = y[R.valid ? row : Nvalid - 1];
+}
+
+__device__ __forceinline__ void issue_x_chunk(XChunkRegs& R,
+                                              const u16* __restrict__ Xbf,
+                                              const int* __restrict__ y,
+                                              long long row0, long long Nvalid) {
+  const int tid = threadIdx.x;
+  #pragma unroll
+  for (int u = 0; u < X_VECS; ++u) {
+    const int i = tid + u * BLOCK;
+    const long long row = row0 + i / (IN / 8);
+    const int c = (i % (IN / 8)) * 8;
+    R.vvalid[u] = row < Nvalid;
+    R.v[u] = *(const bf16x8*)&Xbf[(R.vvalid[u] ? row : Nvalid - 1) * IN + c];
+  }
+  issue_label(R, y, row0, Nvalid);
+}
+
+// the row's label, -1 for a row at or beyond Nvalid
+__device__ __forceinline__ int chunk_label(const XChunkRegs& R) {
+  return R.valid ? R.label : -1;
+}
+
+// Xs row-major + XT transposed, zero batch tail
+__device__ __forceinline__ void store_x_chunk(const XChunkRegs& R, const Lds& L) {
+  const int tid = threadIdx.x;
+  #pragma unroll
+  for (int u = 0; u < X_VECS; ++u) {
+    const int i = tid + u * BLOCK;
     const int r = i / (IN / 8);
     const int c = (i % (IN / 8)) * 8;
-    bf16x8 v;
-    if (row0 + r < Nvalid) {
-      v = *(const bf16x8*)&Xbf[(row0 + r) * IN + c];
-    } else {
-      v = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
-    }
+    const bf16x8 v = R.vvalid[u] ? R.v[u] : (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
     *(bf16x8*)&L.Xs[r][c] = v;
     #pragma unroll
     for (int j = 0; j < 8; ++j) L.XT[c + j][r] = (u16)v[j];
@@ -322,10 +401,12 @@ struct ChunkAcc {
 
 // one 128-row chunk: fwd + bwd, accumulating weight grads in acc_io and
 // bias grads / loss in LDS. b1/b2 point at fp32 biases (any addr space).
+// label/valid describe this thread's softmax row (wrow + lr) and come from
+// issue_x_chunk: the label was loaded with the chunk's X, so no global
+// read sits inside the softmax chain.
 __device__ __forceinline__ void chunk_fwd_bwd(
     const Lds& L, const float* b1, const float* b2,
-    const int* __restrict__ y, long long row0, long long Nvalid, float invBtot,
-    ChunkAcc& acc_io) {
+    const int label, const bool valid, float invBtot, ChunkAcc& acc_io) {
   const int tid = threadIdx.x;
   const int wave = tid >> 6;
   const int l = tid & 63;
@@ -367,8 +448,6 @@ __device__ __forceinline__ void chunk_fwd_bwd(
     acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc[0], 0, 0, 0);
 
     const int row = wrow + lr;
-    const bool valid = (row0 + row) < Nvalid;
-    const int label = valid ? y[row0 + row] : -1;
 
     float logit[1][4], e[1][4];
     head_logits<1>(logit, acc, b2, CLS, lg);
@@ -391,22 +470,21 @@ __device__ __forceinline__ void chunk_fwd_bwd(
     // reduce db2/loss over the 16 row-lanes (lr bits) first, then ONE
     // plain store per (wave, class) into this wave's partial row: the
     // waves are summed in fixed order below, so the step is reproducible
-    // bit for bit (float LDS atomics landed in arrival order)
+    // bit for bit (float LDS atomics landed in arrival order). All five
+    // reductions run first, with every lane active (DPP reads its row
+    // neighbours' registers); the predicated stores follow in one block.
     #pragma unroll
-    for (int bit = 1; bit < 16; bit <<= 1) {
-      #pragma unroll
-      for (int r = 0; r < 4; ++r) db2_acc[r] += __shfl_xor(db2_acc[r], bit, 64);
-      loss_acc += __shfl_xor(loss_acc, bit, 64);
-    }
+    for (int r = 0; r < 4; ++r) db2_acc[r] = row_sum16(db2_acc[r]);
+    loss_acc = row_sum16(loss_acc);
+    // loss_acc now holds the 16-row sum within this lg quarter; fold
+    // the four lg groups (lane bits 4,5) too, then one store per wave
+    loss_acc = group_sum<16>(loss_acc);
+    loss_acc = group_sum<32>(loss_acc);
     if (lr == 0) {
       #pragma unroll
       for (int r = 0; r < 4; ++r) L.part[wave * PART + HID + lg * 4 + r] = db2_acc[r];
+      if (l == 0) L.part[wave * PART + HID + CPAD] = loss_acc;
     }
-    // loss_acc now holds the 16-row sum within this lg quarter; fold
-    // the four lg groups (lane bits 4,5) too, then one store per wave
-    loss_acc += __shfl_xor(loss_acc, 16, 64);
-    loss_acc += __shfl_xor(loss_acc, 32, 64);
-    if (l == 0) L.part[wave * PART + HID + CPAD] = loss_acc;
   }
   // NO __syncthreads here either: dH reads only this wave's rows of
   // DLs and HT. Cross-wave consumers (dW1/dW2 over DLT/HT) wait at the
@@ -414,22 +492,40 @@ __device__ __forceinline__ void chunk_fwd_bwd(
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 
   // ---- dH^T = W2s @ B(DLs);  D: h = mt*16+lg*4+r, row = wrow+lr ------------
-  #pragma unroll
-  for (int mt = 0; mt < HID / 16; ++mt) {
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    const bf16x8 a = *(const bf16x8*)&L.W2s[mt * 16 + lr][lg * 8];
-    const bf16x8 b = *(const bf16x8*)&L.DLs[wrow + lr][lg * 8];
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc, 0, 0, 0);
+  {
+    float db1_acc[HID / 16][4];
     #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int h = mt * 16 + lg * 4 + r;
-      const int row = wrow + lr;
-      const float hv = bf2f(L.HT[h][row]);
-      float dh = hv > 0.f ? acc[r] : 0.f;
-      L.DHT[h][row] = f2bf(dh);
-      // db1[h]: sum this row-block's contribution across the 16 lr lanes
-      dh = row_sum16(dh);
-      if (lr == 0) L.part[wave * PART + h] = dh;
+    for (int mt = 0; mt < HID / 16; ++mt) {
+      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+      const bf16x8 a = *(const bf16x8*)&L.W2s[mt * 16 + lr][lg * 8];
+      const bf16x8 b = *(const bf16x8*)&L.DLs[wrow + lr][lg * 8];
+      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc, 0, 0, 0);
+      #pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int h = mt * 16 + lg * 4 + r;
+        const int row = wrow + lr;
+        const float hv = bf2f(L.HT[h][row]);
+        const float dh = hv > 0.f ? acc[r] : 0.f;
+        L.DHT[h][row] = f2bf(dh);
+        db1_acc[mt][r] = dh;
+      }
+    }
+    // db1[h]: sum this row-block's contribution across the 16 lr lanes.
+    // All eight reductions first, no branch between them, then the
+    // predicated stores in one block.
+    #pragma unroll
+    for (int mt = 0; mt < HID / 16; ++mt) {
+      #pragma unroll
+      for (int r = 0; r < 4; ++r) db1_acc[mt][r] = row_sum16(db1_acc[mt][r]);
+    }
+    if (lr == 0) {
+      #pragma unroll
+      for (int mt = 0; mt < HID / 16; ++mt) {
+        #pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          L.part[wave * PART + mt * 16 + lg * 4 + r] = db1_acc[mt][r];
+        }
+      }
     }
   }
   __syncthreads();   // DHT + per-wave partials complete
@@ -494,16 +590,19 @@ mlp_step_kernel(const u16* __restrict__ Xbf, const int* __restrict__ y, int B,
   if (tid < HID) L.db1[tid] = 0.f;
   if (tid < CPAD) L.db2[tid] = 0.f;
   if (tid == 0) L.loss[0] = 0.f;
+  XChunkRegs xr;
+  issue_x_chunk(xr, Xbf, y, row0, B);
+  const float bias = issue_biases(master + OFF_B1, master + OFF_B2);
   zero_dl_pad(L);
   load_weight_images(L, W1bf, W2bf);
-  load_x_chunk(Xbf, L, row0, B);
-  load_biases(L, master + OFF_B1, master + OFF_B2);
+  store_x_chunk(xr, L);
+  store_biases(bias, L);
   __syncthreads();
 
   ChunkAcc acc;
   acc.dW1 = (f32x4){0.f, 0.f, 0.f, 0.f};
   acc.dW2 = (f32x4){0.f, 0.f, 0.f, 0.f};
-  chunk_fwd_bwd(L, L.b1s, L.b2s, y, row0, B, invBtot, acc);
+  chunk_fwd_bwd(L, L.b1s, L.b2s, chunk_label(xr), xr.valid, invBtot, acc);
 
   {
     const int ht = wave & 1, it = wave >> 1;
@@ -565,33 +664,53 @@ mlp_step_fused_kernel(const u16* __restrict__ Xbf, const int* __restrict__ y,
   const long long row0 = (long long)blockIdx.x * ROWS;
   const int n_wg = gridDim.x;
 
-  if (tid < HID) L.db1[tid] = 0.f;
-  if (tid < CPAD) L.db2[tid] = 0.f;
+  // ---- prologue, phase 1: EVERY global load goes out before the first
+  // wait (after the launch-boundary invalidate each one is a cold round
+  // trip, so they must overlap): X vectors + label, packed images, bias
+  // element, and thread 0's epoch / step counters ----------------------------
+  XChunkRegs xr;
+  WimgRegs wr;
+#ifndef PROBE_SKIP_LOADS
+  issue_x_chunk(xr, Xbf, y, row0, B);
+  if (wimg) issue_weight_images_packed(wr, wimg);
+#else
+  issue_label(xr, y, row0, B);   // timing probe: X and the images stay out
+#endif
+  const float bias = issue_biases(master + OFF_B1, master + OFF_B2);
+  unsigned counter_pre = 0u, t_pre = 0u;
   if (tid == 0) {
-    L.loss[0] = 0.f;
     // read the epoch source BEFORE any workgroup of this launch can have
     // advanced it (the writer only writes after every WG has published,
     // i.e. after every WG has passed this point). BOTH modes use the
     // dedicated launch counter, so mixing fused-Adam and reduce-only
     // launches on one model keeps epochs unique and monotonic; t_dev is
     // read separately for Adam bias correction only.
-    lossu[2] = *counter;
-    lossu[3] = (unsigned)(*t_dev);
+    counter_pre = *counter;
+    t_pre = (unsigned)(*t_dev);
   }
+
+  // ---- phase 2: LDS fills that need no load, then the loaded registers ----
+  if (tid < HID) L.db1[tid] = 0.f;
+  if (tid < CPAD) L.db2[tid] = 0.f;
   zero_dl_pad(L);
 #ifndef PROBE_SKIP_LOADS
-  if (wimg) load_weight_images_packed(L, wimg);
+  if (wimg) store_weight_images_packed(wr, L);
   else load_weight_images(L, W1bf, W2bf);
-  load_x_chunk(Xbf, L, row0, B);
+  store_x_chunk(xr, L);
 #endif
-  load_biases(L, master + OFF_B1, master + OFF_B2);
+  store_biases(bias, L);
+  if (tid == 0) {
+    L.loss[0] = 0.f;
+    lossu[2] = counter_pre;
+    lossu[3] = t_pre;
+  }
   __syncthreads();
 
   ChunkAcc acc;
   acc.dW1 = (f32x4){0.f, 0.f, 0.f, 0.f};
   acc.dW2 = (f32x4){0.f, 0.f, 0.f, 0.f};
 #ifndef PROBE_SKIP_FWDBWD
-  chunk_fwd_bwd(L, L.b1s, L.b2s, y, row0, B, invBtot, acc);
+  chunk_fwd_bwd(L, L.b1s, L.b2s, chunk_label(xr), xr.valid, invBtot, acc);
 #endif
 
   // ---- write this WG's complete partial slab (plain stores, no atomics) ----
@@ -862,9 +981,12 @@ mlp_train_steps_kernel(const u16* __restrict__ Xbf,  // [N][IN] staged bf16
 
     for (int ch = 0; ch < chunks; ++ch) {
       const long long row0 = base + (long long)ch * ROWS;
-      load_x_chunk(Xbf, L, row0, N);
+      XChunkRegs xr;   // the chunk's X vectors and label in one round trip
+      issue_x_chunk(xr, Xbf, y, row0, N);
+      store_x_chunk(xr, L);
       __syncthreads();
-      chunk_fwd_bwd(L, master_s + OFF_B1, master_s + OFF_B2, y, row0, N, invB, acc);
+      chunk_fwd_bwd(L, master_s + OFF_B1, master_s + OFF_B2, chunk_label(xr), xr.valid,
+                    invB, acc);
     }
 
     // ---- fused in-LDS Adam --------------------------------------------------
@@ -1008,6 +1130,30 @@ mlp_predict_kernel(const float* __restrict__ X, int B,
 }
 
 // ---------------------------------------------------------------------------
+// row_sum16 self-test: one wave per row of x [n][64]. Lane l writes the
+// DPP helper's result to out[row][l][0] and the plain __shfl_xor
+// butterfly's (the form row_sum16 replaced, kept only here) to
+// out[row][l][1]; the two must agree bit for bit.
+// ---------------------------------------------------------------------------
+
+extern "C" __global__ void __launch_bounds__(64)
+reduce_selftest_kernel(const float* __restrict__ x, int n,
+                       float* __restrict__ out) {
+  const int row = blockIdx.x;
+  const int l = threadIdx.x;
+  if (row >= n) return;                      // whole wave, never a partial one
+  const float v = x[(long long)row * 64 + l];
+  const float dpp = row_sum16(v);
+  float bfly = v;
+  bfly += __shfl_xor(bfly, 1, 64);
+  bfly += __shfl_xor(bfly, 2, 64);
+  bfly += __shfl_xor(bfly, 4, 64);
+  bfly += __shfl_xor(bfly, 8, 64);
+  out[((long long)row * 64 + l) * 2 + 0] = dpp;
+  out[((long long)row * 64 + l) * 2 + 1] = bfly;
+}
+
+// ---------------------------------------------------------------------------
 // host launchers (extern "C"; stream-ordered, capture-safe)
 // ---------------------------------------------------------------------------
 
@@ -1121,6 +1267,13 @@ void launch_adam_step(float* master, unsigned short* bfmirror, const float* grad
   hipLaunchKernelGGL(adam_step_kernel, dim3(1), dim3(256), 0, stream,
                      master, bfmirror, grads, m, v, t_dev, lr, beta1, beta2, eps,
                      wimg);
+}
+
+void launch_reduce_selftest(const float* x, int n, float* out,
+                            hipStream_t stream) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(reduce_selftest_kernel, dim3(n), dim3(64), 0, stream, x, n,
+                     out);
 }
 
 }  // extern "C"

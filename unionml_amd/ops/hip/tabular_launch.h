@@ -82,6 +82,10 @@ void launch_adam_step(float* master, unsigned short* bfmirror, const float* grad
                       float* m, float* v, int* t_dev, float lr, float beta1,
                       float beta2, float eps, unsigned short* wimg,
                       hipStream_t stream);
+// x [n][64] fp32, one wave per row -> out [n][64][2]: the in-row sum of 16
+// by the kernels' DPP helper, and by the plain shuffle butterfly
+void launch_reduce_selftest(const float* x, int n, float* out,
+                            hipStream_t stream);
 
 // ---- tabular_gen.hip (any geometry) -----------------------------------------
 

@@ -3,6 +3,8 @@
 // tabular_launch.h). All launches go to the current torch stream so they
 // compose with torch.cuda.graphs capture and RCCL work.
 
+#include <climits>
+
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
@@ -199,6 +201,16 @@ void adam_step(torch::Tensor master, torch::Tensor bfmirror, torch::Tensor grads
                    digits_wimg_ptr(wimg), current_stream());
 }
 
+torch::Tensor reduce_selftest(torch::Tensor x) {
+  check(x, torch::kFloat32, "x");
+  TORCH_CHECK(x.dim() == 2 && x.size(1) == 64, "x must be [n][64]");
+  TORCH_CHECK(x.size(0) <= INT_MAX, "too many rows");
+  torch::Tensor out = torch::empty({x.size(0), 64, 2}, x.options());
+  launch_reduce_selftest(x.data_ptr<float>(), (int)x.size(0),
+                         out.data_ptr<float>(), current_stream());
+  return out;
+}
+
 // ---------------------------------------------------------------------------
 // generalized-geometry (any in_features/hidden/classes) entry points
 // ---------------------------------------------------------------------------
@@ -314,6 +326,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("master"), py::arg("bfmirror"), py::arg("grads"), py::arg("m"),
         py::arg("v"), py::arg("t_dev"), py::arg("lr"), py::arg("beta1"),
         py::arg("beta2"), py::arg("eps"), py::arg("wimg") = c10::nullopt);
+  m.def("reduce_selftest", &reduce_selftest,
+        "x [n][64] -> [n][64][2]: in-row sums of 16 by the DPP helper and by "
+        "the shuffle butterfly (must be bit-equal)",
+        py::arg("x"));
   m.def("mlp_step_gen", &mlp_step_gen,
         "generalized fused step: any (in,hid,cls) geometry; double-buffered "
         "K-tiled MFMA fwd+bwd producing per-WG gradient slabs",
