@@ -14,6 +14,18 @@ typedef __attribute__((ext_vector_type(8))) short bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef unsigned short u16;
 
+// Heads of the generalized kernels (tabular_gen.hip), a compile-time
+// choice: softmax + cross-entropy over classes, or squared error over
+// continuous targets.
+constexpr int HEAD_XENT = 0;
+constexpr int HEAD_REG = 1;
+
+// a row's target as the step kernel reads it: an int class label, or a row
+// of fp32 standardized targets padded to CPAD columns
+template <int HEAD> struct head_target { typedef int type; };
+template <> struct head_target<HEAD_REG> { typedef float type; };
+template <int HEAD> using head_target_t = typename head_target<HEAD>::type;
+
 __device__ __forceinline__ float bf2f(u16 v) {
   union { float f; unsigned u; } c;
   c.u = ((unsigned)v) << 16;

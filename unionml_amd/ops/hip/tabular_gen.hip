@@ -32,6 +32,12 @@
 //     MFMA tiles): the wave-shuffle softmax (tabular_common.h head_*)
 //     masks c >= cls and folds across the register-resident
 //     class-tile axis.
+//   * The head is a compile-time choice of the step and the predict
+//     kernel (HEAD_XENT / HEAD_REG): the regression head swaps the
+//     softmax/xent epilogue for squared error over cls = T continuous
+//     targets and the argmax for the de-standardized outputs. Everything
+//     else (fwd1, dH, dW2, dW1, slabs, reduce+Adam) is shared, and
+//     every <HID, RT, CPAD> instantiation exists for both heads.
 //
 // All launches are stream-ordered and hipGraph-capturable; the Adam
 // step counter lives in device memory so bias correction is exact
@@ -257,10 +263,15 @@ __device__ __forceinline__ void zero_dl_pad(const G& L) {
 // fused generalized step kernel
 // ---------------------------------------------------------------------------
 
-template <int HID, int RT, int CP>
+// The head is a compile-time choice (tabular_common.h HEAD_*): the
+// softmax/xent classifier, or squared error over cls = T continuous
+// targets. What a row's target is differs with it: an int label y[N], or
+// fp32 standardized targets Yt[N][CPAD], pad columns zero. Everything
+// outside the fwd2 epilogue is shared.
+template <int HID, int RT, int CP, int HEAD = HEAD_XENT>
 __global__ void __launch_bounds__(512)
 mlp_step_gen_kernel(const u16* __restrict__ Xbf,   // [N][inp] staged bf16 (zero-padded)
-                    const int* __restrict__ y, int B,
+                    const head_target_t<HEAD>* __restrict__ y, int B,
                     int inp, int cls,
                     const u16* __restrict__ wimg,  // packed weight images
                     const float* __restrict__ master,  // biases prefetch
@@ -367,8 +378,22 @@ mlp_step_gen_kernel(const u16* __restrict__ Xbf,   // [N][inp] staged bf16 (zero
   // ---- fwd2: L^T = W2T @ B(Hs); wave-shuffle softmax + xent over NCT
   // class tiles (classes <= 16: one MFMA tile; 17..32: two tiles, the
   // max/sum folds across the register-resident tile axis first, then
-  // the 4 lane-groups) ------------------------------------------------------
+  // the 4 lane-groups). The regression head swaps the softmax block for
+  // dz = (z - y) / Btot; the DLs/DLT dual stores, the db2 row sums and the
+  // loss fold below are the same code for both heads ------------------------
   for (int t2 = wave; t2 < RT / 16; t2 += G::WAVES) {
+    // regression: this lane's targets, 4 consecutive columns per class
+    // tile (one aligned 16-byte load each), issued BEFORE the MFMAs so
+    // the round trip hides under them. A tail row loads row B-1 and is
+    // masked after the wait: the load sits under no branch.
+    [[maybe_unused]] f32x4 yt[G::NCT];
+    if constexpr (HEAD == HEAD_REG) {
+      const long long yrow = min(row0 + t2 * 16 + lr_, (long long)B - 1);
+      #pragma unroll
+      for (int ct = 0; ct < G::NCT; ++ct) {
+        yt[ct] = *(const f32x4*)&y[yrow * G::CPAD + ct * 16 + lg * 4];
+      }
+    }
     f32x4 acc[G::NCT];
     #pragma unroll
     for (int ct = 0; ct < G::NCT; ++ct) {
@@ -382,28 +407,51 @@ mlp_step_gen_kernel(const u16* __restrict__ Xbf,   // [N][inp] staged bf16 (zero
     }
     const int row = t2 * 16 + lr_;
     const bool valid = (row0 + row) < (long long)B;
-    const int label = valid ? y[row0 + row] : -1;
-
-    float logit[G::NCT][4], e[G::NCT][4];
-    head_logits<G::NCT>(logit, acc, L.b2s, cls, lg);
-    const float mx = head_row_max<G::NCT>(logit);
-    const float ssum = head_exp_sum<G::NCT>(e, logit, mx, cls, lg);
-    const float rs = fast_rcp(ssum);
-    const float logs = __logf(ssum);
     float db2_acc[G::NCT][4];
     float loss_acc = 0.f;
-    #pragma unroll
-    for (int ct = 0; ct < G::NCT; ++ct) {
+    if constexpr (HEAD == HEAD_REG) {
+      // dz = (z - y) / Btot on real targets of valid rows, exactly 0 on
+      // pad columns and tail rows (selects, so a pad can leak nothing);
+      // row loss 0.5 / Btot * sum (z - y)^2, folded over registers here
+      // and over the lane groups below
       #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int c = ct * 16 + lg * 4 + r;
-        const float dl =
-            valid ? (e[ct][r] * rs - (c == label ? 1.f : 0.f)) * invBtot : 0.f;
-        const u16 dlb = f2bf(dl);
-        L.DLs[row][c] = dlb;
-        L.DLT[c][row] = dlb;
-        db2_acc[ct][r] = dl;
-        if (valid && c == label) loss_acc = -(logit[ct][r] - mx - logs) * invBtot;
+      for (int ct = 0; ct < G::NCT; ++ct) {
+        #pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int c = ct * 16 + lg * 4 + r;
+          const bool on = valid && c < cls;
+          const float d = (acc[ct][r] + L.b2s[c]) - yt[ct][r];
+          const float dz = on ? d * invBtot : 0.f;
+          const u16 dzb = f2bf(dz);
+          L.DLs[row][c] = dzb;
+          L.DLT[c][row] = dzb;
+          db2_acc[ct][r] = dz;
+          loss_acc += on ? d * d : 0.f;
+        }
+      }
+      loss_acc *= 0.5f * invBtot;
+    } else {
+      const int label = valid ? y[row0 + row] : -1;
+
+      float logit[G::NCT][4], e[G::NCT][4];
+      head_logits<G::NCT>(logit, acc, L.b2s, cls, lg);
+      const float mx = head_row_max<G::NCT>(logit);
+      const float ssum = head_exp_sum<G::NCT>(e, logit, mx, cls, lg);
+      const float rs = fast_rcp(ssum);
+      const float logs = __logf(ssum);
+      #pragma unroll
+      for (int ct = 0; ct < G::NCT; ++ct) {
+        #pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int c = ct * 16 + lg * 4 + r;
+          const float dl =
+              valid ? (e[ct][r] * rs - (c == label ? 1.f : 0.f)) * invBtot : 0.f;
+          const u16 dlb = f2bf(dl);
+          L.DLs[row][c] = dlb;
+          L.DLT[c][row] = dlb;
+          db2_acc[ct][r] = dl;
+          if (valid && c == label) loss_acc = -(logit[ct][r] - mx - logs) * invBtot;
+        }
       }
     }
     // in-row sums first (DPP, every lane active), predicated atomics after
@@ -600,7 +648,21 @@ reduce_adam_gen_kernel(const float* __restrict__ slabs, int n_wg,
 // generalized fused predict: standardize + fwd + argmax (+softmax)
 // ---------------------------------------------------------------------------
 
-template <int HID, int RT, int CP>
+// What the predict epilogue needs besides its fp32 output matrix, per
+// head. The classifier writes the argmax to int preds[B] (and softmax
+// probabilities to the optional out [B][cls]); the regression head writes
+// out[row][c] = z * y_scale[c] + y_mean[c], the target de-standardization
+// fused into the epilogue, into out [B][ldo], ldo >= cls. The classifier's
+// argument list (int* preds, float* probs) stays what it was.
+struct RegAffine {
+  const float* y_mean;   // [cls]
+  const float* y_scale;  // [cls]
+  int ldo;
+};
+template <int HEAD> struct predict_aux { typedef int* __restrict__ type; };
+template <> struct predict_aux<HEAD_REG> { typedef RegAffine type; };
+
+template <int HID, int RT, int CP, int HEAD = HEAD_XENT>
 __global__ void __launch_bounds__(512)
 mlp_predict_gen_kernel(const float* __restrict__ X,  // [B][draw] raw fp32
                        int B, int draw, int inp, int cls,
@@ -608,8 +670,8 @@ mlp_predict_gen_kernel(const float* __restrict__ X,  // [B][draw] raw fp32
                        const float* __restrict__ invstd,
                        const u16* __restrict__ wimg,
                        const float* __restrict__ master,  // biases
-                       int* __restrict__ preds,
-                       float* __restrict__ probs /* optional [B][cls] */) {
+                       typename predict_aux<HEAD>::type aux,
+                       float* __restrict__ out) {
   using G = GG<HID, RT, CP>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   G L;
@@ -684,7 +746,22 @@ mlp_predict_gen_kernel(const float* __restrict__ X,  // [B][draw] raw fp32
   }
   __syncthreads();
 
-  // fwd2 + argmax / softmax over NCT class tiles
+  // regression: this lane's de-standardization pairs, fetched once ahead
+  // of the MFMAs (index clamped instead of branched; c >= cls never stores)
+  [[maybe_unused]] float ysc[G::NCT][4], ymn[G::NCT][4];
+  if constexpr (HEAD == HEAD_REG) {
+    #pragma unroll
+    for (int ct = 0; ct < G::NCT; ++ct) {
+      #pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int c = min(ct * 16 + lg * 4 + r, cls - 1);
+        ysc[ct][r] = aux.y_scale[c];
+        ymn[ct][r] = aux.y_mean[c];
+      }
+    }
+  }
+
+  // fwd2 + argmax / softmax (or the regression outputs) over NCT class tiles
   for (int t2 = wave; t2 < RT / 16; t2 += G::WAVES) {
     f32x4 acc[G::NCT];
     #pragma unroll
@@ -698,21 +775,37 @@ mlp_predict_gen_kernel(const float* __restrict__ X,  // [B][draw] raw fp32
       }
     }
     const int row = t2 * 16 + lr;
-    float best;
-    int bcol;
-    float logit[G::NCT][4];
-    head_logits<G::NCT>(logit, acc, L.b2s, cls, lg);
-    head_argmax<G::NCT>(logit, cls, lg, best, bcol);
-    if (lg == 0 && row0 + row < B) preds[row0 + row] = bcol;
-    if (probs != nullptr) {
-      float e[G::NCT][4];
-      const float rs = fast_rcp(head_exp_sum<G::NCT>(e, logit, best, cls, lg));
+    if constexpr (HEAD == HEAD_REG) {
       #pragma unroll
       for (int ct = 0; ct < G::NCT; ++ct) {
         #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int c = ct * 16 + lg * 4 + r;
-          if (c < cls && row0 + row < B) probs[(row0 + row) * cls + c] = e[ct][r] * rs;
+          if (c < cls && row0 + row < B) {
+            out[(row0 + row) * aux.ldo + c] =
+                (acc[ct][r] + L.b2s[c]) * ysc[ct][r] + ymn[ct][r];
+          }
+        }
+      }
+    } else {
+      int* __restrict__ preds = aux;
+      float* __restrict__ probs = out;
+      float best;
+      int bcol;
+      float logit[G::NCT][4];
+      head_logits<G::NCT>(logit, acc, L.b2s, cls, lg);
+      head_argmax<G::NCT>(logit, cls, lg, best, bcol);
+      if (lg == 0 && row0 + row < B) preds[row0 + row] = bcol;
+      if (probs != nullptr) {
+        float e[G::NCT][4];
+        const float rs = fast_rcp(head_exp_sum<G::NCT>(e, logit, best, cls, lg));
+        #pragma unroll
+        for (int ct = 0; ct < G::NCT; ++ct) {
+          #pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int c = ct * 16 + lg * 4 + r;
+            if (c < cls && row0 + row < B) probs[(row0 + row) * cls + c] = e[ct][r] * rs;
+          }
         }
       }
     }
@@ -756,48 +849,49 @@ __global__ void bump_t_kernel(int* __restrict__ t_dev) { ++(*t_dev); }
 
 namespace {
 
-template <int HID, int RT, int CP>
-int launch_step_gen_t(const unsigned short* Xbf, const int* y, int B, int inp,
-                      int cls, const unsigned short* wimg, const float* master,
-                      float* slabs, int slab_stride, int max_slabs,
-                      float invBtot, hipStream_t stream) {
+template <int HID, int RT, int CP, int HEAD>
+int launch_step_gen_t(const unsigned short* Xbf, const head_target_t<HEAD>* y,
+                      int B, int inp, int cls, const unsigned short* wimg,
+                      const float* master, float* slabs, int slab_stride,
+                      int max_slabs, float invBtot, hipStream_t stream) {
   using G = gen::GG<HID, RT, CP>;
   const int blocks = (B + RT - 1) / RT;
   if (blocks > max_slabs) return -1;
   static int done = 0;
   if (!done) {
-    if (hipFuncSetAttribute((const void*)gen::mlp_step_gen_kernel<HID, RT, CP>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize,
-                            G::TOTAL) != hipSuccess) {
+    if (hipFuncSetAttribute(
+            (const void*)gen::mlp_step_gen_kernel<HID, RT, CP, HEAD>,
+            hipFuncAttributeMaxDynamicSharedMemorySize, G::TOTAL) != hipSuccess) {
       return -2;
     }
     done = 1;
   }
-  hipLaunchKernelGGL((gen::mlp_step_gen_kernel<HID, RT, CP>), dim3(blocks),
+  hipLaunchKernelGGL((gen::mlp_step_gen_kernel<HID, RT, CP, HEAD>), dim3(blocks),
                      dim3(G::BLOCK), G::TOTAL, stream, Xbf, y, B, inp, cls, wimg,
                      master, slabs, slab_stride, invBtot);
   return 0;
 }
 
-template <int HID, int RT, int CP>
+template <int HID, int RT, int CP, int HEAD>
 int launch_predict_gen_t(const float* X, int B, int draw, int inp, int cls,
                          const float* mean, const float* invstd,
                          const unsigned short* wimg, const float* master,
-                         int* preds, float* probs, hipStream_t stream) {
+                         typename gen::predict_aux<HEAD>::type aux, float* out,
+                         hipStream_t stream) {
   using G = gen::GG<HID, RT, CP>;
   static int done = 0;
   if (!done) {
     if (hipFuncSetAttribute(
-            (const void*)gen::mlp_predict_gen_kernel<HID, RT, CP>,
+            (const void*)gen::mlp_predict_gen_kernel<HID, RT, CP, HEAD>,
             hipFuncAttributeMaxDynamicSharedMemorySize, G::TOTAL) != hipSuccess) {
       return -2;
     }
     done = 1;
   }
   const int blocks = (B + RT - 1) / RT;
-  hipLaunchKernelGGL((gen::mlp_predict_gen_kernel<HID, RT, CP>), dim3(blocks),
-                     dim3(G::BLOCK), G::TOTAL, stream, X, B, draw, inp, cls, mean,
-                     invstd, wimg, master, preds, probs);
+  hipLaunchKernelGGL((gen::mlp_predict_gen_kernel<HID, RT, CP, HEAD>),
+                     dim3(blocks), dim3(G::BLOCK), G::TOTAL, stream, X, B, draw,
+                     inp, cls, mean, invstd, wimg, master, aux, out);
   return 0;
 }
 
@@ -812,9 +906,9 @@ int launch_mlp_step_gen(const unsigned short* Xbf, const int* y, int B, int inp,
   if (inp % 32 != 0 || cls > 32) return -3;
   #define STEP_CASE(H, R, C)                                                  \
     if (hid == H && rt == R && cls <= C && (C == 16 ? cls <= 16 : cls > 16))  \
-      return launch_step_gen_t<H, R, C>(Xbf, y, B, inp, cls, wimg, master,    \
-                                        slabs, slab_stride, max_slabs,        \
-                                        invBtot, stream);
+      return launch_step_gen_t<H, R, C, HEAD_XENT>(                           \
+          Xbf, y, B, inp, cls, wimg, master, slabs, slab_stride, max_slabs,   \
+          invBtot, stream);
   STEP_CASE(32, 128, 16)
   STEP_CASE(32, 64, 16)
   STEP_CASE(64, 128, 16)
@@ -827,6 +921,34 @@ int launch_mlp_step_gen(const unsigned short* Xbf, const int* y, int B, int inp,
   STEP_CASE(128, 64, 32)
   STEP_CASE(256, 32, 32)
   #undef STEP_CASE
+  return -3;
+}
+
+// regression head: the same <HID, RT, CPAD> list as STEP_CASE above, one
+// for one (a regressor has no specialized kernels: every shape lands here)
+int launch_mlp_step_reg_gen(const unsigned short* Xbf, const float* Yt, int B,
+                            int inp, int hid, int targets, int rt,
+                            const unsigned short* wimg, const float* master,
+                            float* slabs, int slab_stride, int max_slabs,
+                            float invBtot, hipStream_t stream) {
+  if (inp % 32 != 0 || targets < 1 || targets > 32 || B < 1) return -3;
+  #define STEP_REG_CASE(H, R, C)                                              \
+    if (hid == H && rt == R && (C == 16 ? targets <= 16 : targets > 16))      \
+      return launch_step_gen_t<H, R, C, HEAD_REG>(                            \
+          Xbf, Yt, B, inp, targets, wimg, master, slabs, slab_stride,         \
+          max_slabs, invBtot, stream);
+  STEP_REG_CASE(32, 128, 16)
+  STEP_REG_CASE(32, 64, 16)
+  STEP_REG_CASE(64, 128, 16)
+  STEP_REG_CASE(64, 64, 16)
+  STEP_REG_CASE(128, 64, 16)
+  STEP_REG_CASE(128, 32, 16)
+  STEP_REG_CASE(256, 32, 16)
+  STEP_REG_CASE(32, 128, 32)
+  STEP_REG_CASE(64, 128, 32)
+  STEP_REG_CASE(128, 64, 32)
+  STEP_REG_CASE(256, 32, 32)
+  #undef STEP_REG_CASE
   return -3;
 }
 
@@ -853,8 +975,9 @@ int launch_mlp_predict_gen(const float* X, int B, int draw, int inp, int hid,
   if (inp % 32 != 0 || cls > 32) return -3;
   #define PRED_CASE(H, R, C)                                                  \
     if (hid == H && (C == 16 ? cls <= 16 : cls > 16))                         \
-      return launch_predict_gen_t<H, R, C>(X, B, draw, inp, cls, mean, invstd,\
-                                           wimg, master, preds, probs, stream);
+      return launch_predict_gen_t<H, R, C, HEAD_XENT>(                        \
+          X, B, draw, inp, cls, mean, invstd, wimg, master, preds, probs,     \
+          stream);
   PRED_CASE(32, 128, 16)
   PRED_CASE(64, 128, 16)
   PRED_CASE(128, 64, 16)
@@ -864,6 +987,33 @@ int launch_mlp_predict_gen(const float* X, int B, int draw, int inp, int hid,
   PRED_CASE(128, 64, 32)
   PRED_CASE(256, 32, 32)
   #undef PRED_CASE
+  return -3;
+}
+
+// regression head: the same <HID, RT, CPAD> list as PRED_CASE above
+int launch_mlp_predict_reg_gen(const float* X, int B, int draw, int inp, int hid,
+                               int targets, const float* mean,
+                               const float* invstd, const unsigned short* wimg,
+                               const float* master, const float* y_mean,
+                               const float* y_scale, float* out, int ldo,
+                               hipStream_t stream) {
+  if (inp % 32 != 0 || targets < 1 || targets > 32 || ldo < targets || B < 1) {
+    return -3;
+  }
+  #define PRED_REG_CASE(H, R, C)                                              \
+    if (hid == H && (C == 16 ? targets <= 16 : targets > 16))                 \
+      return launch_predict_gen_t<H, R, C, HEAD_REG>(                         \
+          X, B, draw, inp, targets, mean, invstd, wimg, master,               \
+          gen::RegAffine{y_mean, y_scale, ldo}, out, stream);
+  PRED_REG_CASE(32, 128, 16)
+  PRED_REG_CASE(64, 128, 16)
+  PRED_REG_CASE(128, 64, 16)
+  PRED_REG_CASE(256, 32, 16)
+  PRED_REG_CASE(32, 128, 32)
+  PRED_REG_CASE(64, 128, 32)
+  PRED_REG_CASE(128, 64, 32)
+  PRED_REG_CASE(256, 32, 32)
+  #undef PRED_REG_CASE
   return -3;
 }
 

@@ -112,4 +112,20 @@ void launch_adam_step_gen(float* master, unsigned short* bfmirror,
                           float beta1, float beta2, float eps,
                           unsigned short* wimg, hipStream_t stream);
 
+// regression head (squared error over 1..32 targets): same slabs, same
+// return codes. Yt [B][cpad] fp32 standardized targets, pad columns zero,
+// 16-byte aligned; out [B][ldo] fp32, ldo >= targets, receives
+// z * y_scale + y_mean in the first `targets` columns.
+int launch_mlp_step_reg_gen(const unsigned short* Xbf, const float* Yt, int B,
+                            int inp, int hid, int targets, int rt,
+                            const unsigned short* wimg, const float* master,
+                            float* slabs, int slab_stride, int max_slabs,
+                            float invBtot, hipStream_t stream);
+int launch_mlp_predict_reg_gen(const float* X, int B, int draw, int inp, int hid,
+                               int targets, const float* mean,
+                               const float* invstd, const unsigned short* wimg,
+                               const float* master, const float* y_mean,
+                               const float* y_scale, float* out, int ldo,
+                               hipStream_t stream);
+
 }  // extern "C"

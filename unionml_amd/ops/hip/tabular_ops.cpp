@@ -301,6 +301,82 @@ void adam_step_gen(torch::Tensor master, torch::Tensor bfmirror,
                        current_stream());
 }
 
+// ---------------------------------------------------------------------------
+// regression head of the generalized kernels (squared error, 1..32 targets)
+// ---------------------------------------------------------------------------
+
+bool mlp_step_reg_gen(torch::Tensor Xbf, torch::Tensor Yt, int64_t hid,
+                      int64_t targets, int64_t rt, torch::Tensor wimg,
+                      torch::Tensor master, torch::Tensor slabs, double invBtot) {
+  check(Xbf, torch::kBFloat16, "Xbf");
+  check(Yt, torch::kFloat32, "Yt");
+  check(wimg, torch::kBFloat16, "wimg");
+  check(master, torch::kFloat32, "master");
+  check(slabs, torch::kFloat32, "slabs");
+  TORCH_CHECK(targets >= 1 && targets <= 32, "targets must be 1..32");
+  TORCH_CHECK(Xbf.dim() == 2 && Xbf.size(0) >= 1, "Xbf must be [B][inp], B >= 1");
+  const int inp = (int)Xbf.size(1);
+  const int cpad = targets <= 16 ? 16 : 32;
+  const int nparam = gen_nparam(inp, hid, cpad);
+  TORCH_CHECK(inp % 32 == 0, "staged input width must be a multiple of 32");
+  // the kernel reads a row's targets as aligned 16-byte groups of a
+  // [B][cpad] matrix (TabularMLPRegressor.stage_targets builds it)
+  TORCH_CHECK(Yt.dim() == 2 && Yt.size(0) == Xbf.size(0) && Yt.size(1) == cpad,
+              "Yt must be [B][", cpad, "] standardized targets, zero-padded");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(Yt.data_ptr()) % 16 == 0,
+              "Yt must be 16-byte aligned");
+  TORCH_CHECK(master.numel() >= nparam, "master too small for geometry");
+  TORCH_CHECK(wimg.numel() >= (int64_t)hid * inp + hid * 32 + cpad * hid,
+              "wimg too small for geometry");
+  TORCH_CHECK(slabs.dim() == 2 && slabs.size(1) >= nparam + 2,
+              "slabs must be [n][>= nparam+2]");
+  const int rc = launch_mlp_step_reg_gen(
+      bf16_ptr(Xbf), Yt.data_ptr<float>(), (int)Xbf.size(0), inp, (int)hid,
+      (int)targets, (int)rt, bf16_ptr(wimg), master.data_ptr<float>(),
+      slabs.data_ptr<float>(), (int)slabs.size(1), (int)slabs.size(0),
+      (float)invBtot, current_stream());
+  TORCH_CHECK(rc != -2, "mlp_step_reg_gen: hipFuncSetAttribute(LDS) failed");
+  TORCH_CHECK(rc != -3, "mlp_step_reg_gen: unsupported geometry (hid=", hid,
+              " inp=", inp, " targets=", targets, " rt=", rt, ")");
+  return rc == 0;  // false -> more WGs than slab rows, caller re-sizes
+}
+
+void mlp_predict_reg_gen(torch::Tensor X, int64_t inp, int64_t hid,
+                         int64_t targets, torch::Tensor mean,
+                         torch::Tensor invstd, torch::Tensor wimg,
+                         torch::Tensor master, torch::Tensor y_mean,
+                         torch::Tensor y_scale, torch::Tensor out) {
+  check(X, torch::kFloat32, "X");
+  check(mean, torch::kFloat32, "mean");
+  check(invstd, torch::kFloat32, "invstd");
+  check(wimg, torch::kBFloat16, "wimg");
+  check(master, torch::kFloat32, "master");
+  check(y_mean, torch::kFloat32, "y_mean");
+  check(y_scale, torch::kFloat32, "y_scale");
+  check(out, torch::kFloat32, "out");
+  TORCH_CHECK(targets >= 1 && targets <= 32, "targets must be 1..32");
+  const int cpad = targets <= 16 ? 16 : 32;
+  TORCH_CHECK(X.dim() == 2 && X.size(0) >= 1 && X.size(1) <= inp,
+              "X must be [B][<= inp], B >= 1");
+  TORCH_CHECK(mean.numel() == X.size(1) && invstd.numel() == X.size(1),
+              "mean/invstd must match raw feature width");
+  TORCH_CHECK(master.numel() >= gen_nparam(inp, hid, cpad),
+              "master too small for geometry");
+  TORCH_CHECK(wimg.numel() >= hid * inp + hid * 32 + cpad * hid,
+              "wimg too small for geometry");
+  TORCH_CHECK(y_mean.numel() == targets && y_scale.numel() == targets,
+              "y_mean/y_scale must hold one entry per target");
+  TORCH_CHECK(out.dim() == 2 && out.size(0) >= X.size(0) && out.size(1) >= targets,
+              "out must be [>= B][>= targets]");
+  const int rc = launch_mlp_predict_reg_gen(
+      X.data_ptr<float>(), (int)X.size(0), (int)X.size(1), (int)inp, (int)hid,
+      (int)targets, mean.data_ptr<float>(), invstd.data_ptr<float>(),
+      bf16_ptr(wimg), master.data_ptr<float>(), y_mean.data_ptr<float>(),
+      y_scale.data_ptr<float>(), out.data_ptr<float>(), (int)out.size(1),
+      current_stream());
+  TORCH_CHECK(rc == 0, "mlp_predict_reg_gen: unsupported geometry or LDS failure");
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // specialized (digits) layout numbers the host side stages buffers with
   m.attr("WIMG_N") = DIGITS_WIMG_N;   // packed weight image, bf16 elements
@@ -355,4 +431,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("v"), py::arg("t_dev"), py::arg("inp"), py::arg("hid"),
         py::arg("cpad"), py::arg("lr"), py::arg("beta1"), py::arg("beta2"),
         py::arg("eps"), py::arg("wimg") = c10::nullopt);
+  m.def("mlp_step_reg_gen", &mlp_step_reg_gen,
+        "generalized fused step with the regression head: squared error "
+        "over 1..32 standardized targets Yt [B][cpad]; same slabs as "
+        "mlp_step_gen",
+        py::arg("Xbf"), py::arg("Yt"), py::arg("hid"), py::arg("targets"),
+        py::arg("rt"), py::arg("wimg"), py::arg("master"), py::arg("slabs"),
+        py::arg("invBtot"));
+  m.def("mlp_predict_reg_gen", &mlp_predict_reg_gen,
+        "generalized fused standardize+fwd with the regression head: "
+        "out[b][t] = z * y_scale[t] + y_mean[t]",
+        py::arg("X"), py::arg("inp"), py::arg("hid"), py::arg("targets"),
+        py::arg("mean"), py::arg("invstd"), py::arg("wimg"), py::arg("master"),
+        py::arg("y_mean"), py::arg("y_scale"), py::arg("out"));
 }

@@ -18,6 +18,11 @@ NPARAM = 2608
 SUPPORTED_HID = (32, 64, 128, 256)
 MAX_CLASSES = 32
 
+# heads of the generalized kernels: softmax + cross-entropy over classes, or
+# squared error over continuous targets (TabularMLPRegressor)
+HEAD_CLASSIFIER = "classifier"
+HEAD_REGRESSION = "regression"
+
 
 class Geometry:
     """Padded kernel geometry for an arbitrary (in_features, hidden,
@@ -29,12 +34,27 @@ class Geometry:
     MFMA tiles. Zero padding is mathematically exact under Adam-from-zero-init
     (zero init + zero gradient -> zero update), so the padded model's
     real sub-block evolves identically to the unpadded math.
+
+    ``head="regression"`` reads the third number as the count of
+    continuous targets (1..32, a single target included); it is kept in
+    ``.classes`` so the flat layout is the classifier's. A regression
+    geometry never takes the specialized kernels and compares unequal to
+    a classifier geometry of the same numbers.
     """
 
-    def __init__(self, in_features: int, hidden: int, classes: int):
-        if in_features < 1 or hidden < 1 or classes < 2:
+    def __init__(self, in_features: int, hidden: int, classes: int,
+                 head: str = HEAD_CLASSIFIER):
+        if head not in (HEAD_CLASSIFIER, HEAD_REGRESSION):
+            raise ValueError(f"unknown head {head!r}")
+        min_out = 1 if head == HEAD_REGRESSION else 2
+        if in_features < 1 or hidden < 1 or classes < min_out:
             raise ValueError(f"bad geometry ({in_features}, {hidden}, {classes})")
         if classes > MAX_CLASSES:
+            if head == HEAD_REGRESSION:
+                raise ValueError(
+                    f"targets={classes} unsupported: the fused head spans at most "
+                    f"two MFMA tiles ({MAX_CLASSES} targets max)"
+                )
             raise ValueError(
                 f"classes={classes} unsupported: the fused classifier head spans "
                 f"at most two MFMA tiles ({MAX_CLASSES} classes max)"
@@ -43,6 +63,7 @@ class Geometry:
             raise ValueError(
                 f"hidden={hidden} exceeds the largest compiled width {SUPPORTED_HID[-1]}"
             )
+        self.head = head
         self.in_features = in_features
         self.hidden = hidden
         self.classes = classes
@@ -58,18 +79,25 @@ class Geometry:
         # packed weight images: W1T [hid][inp] + W2s [hid][32] + W2T [cpad][hid]
         self.wimg_n = self.hid * self.inp + self.hid * 32 + self.cpad * self.hid
         # the hand-tuned specialized kernel path covers exactly this shape
-        self.is_specialized = (in_features, hidden, classes) == (64, 32, 10)
+        self.is_specialized = (
+            head == HEAD_CLASSIFIER and (in_features, hidden, classes) == (64, 32, 10)
+        )
+
+    def __setstate__(self, state):
+        state.setdefault("head", HEAD_CLASSIFIER)   # pickles from before the heads
+        self.__dict__.update(state)
 
     def __repr__(self):
+        tag = "" if self.head == HEAD_CLASSIFIER else f", head={self.head}"
         return (
             f"Geometry({self.in_features}->{self.hidden}->{self.classes}, "
-            f"padded {self.inp}x{self.hid}x{self.cpad}, nparam={self.nparam})"
+            f"padded {self.inp}x{self.hid}x{self.cpad}, nparam={self.nparam}{tag})"
         )
 
     def __eq__(self, other):
         return isinstance(other, Geometry) and (
-            (self.in_features, self.hidden, self.classes)
-            == (other.in_features, other.hidden, other.classes)
+            (self.in_features, self.hidden, self.classes, self.head)
+            == (other.in_features, other.hidden, other.classes, other.head)
         )
 
 
@@ -249,6 +277,75 @@ def mlp_predict_g(
     if return_probs:
         return preds, torch.softmax(logits, dim=1)
     return preds
+
+
+def mlp_step_reg_g(
+    g: Geometry,
+    Xbf: torch.Tensor,  # [B][inp] staged bf16 (zero-padded)
+    Yt: torch.Tensor,   # [B][cpad] fp32 standardized targets (zero-padded)
+    W1bf: torch.Tensor,
+    W2bf: torch.Tensor,
+    master: torch.Tensor,
+    grads: torch.Tensor,
+    invBtot: float,
+) -> None:
+    """Squared-error twin of mlp_step_g, mirroring the regression head of
+    mlp_step_gen_kernel: loss = 0.5 * invBtot * sum_{b, c < T} (z - y)^2,
+    H rounded to bf16 before layer 2, dz and dH rounded for the products
+    they feed; db2 sums the unrounded dz as the kernel does."""
+    _, b1, _, b2 = unpack_master_g(g, master)
+    T = g.classes
+    X = Xbf.float()
+    W1 = W1bf.float()
+    W2 = W2bf.float()
+    H = torch.relu(X @ W1 + b1)
+    Hbf = H.bfloat16().float()
+    z = Hbf @ W2 + b2
+    d = torch.zeros_like(z)
+    d[:, :T] = z[:, :T] - Yt.float()[:, :T]
+    dz = d * invBtot
+    loss = float(0.5 * invBtot * (d * d).sum())
+
+    dz_bf = dz.bfloat16().float()
+    dH = dz_bf @ W2.T
+    dH = dH * (Hbf > 0)
+    dH_bf = dH.bfloat16().float()
+
+    dW2 = Hbf.T @ dz_bf
+    db2 = dz.sum(dim=0)
+    dW1 = X.T @ dH_bf
+    db1 = dH_bf.sum(dim=0)
+
+    grads[g.off_w1 : g.off_w1 + g.inp * g.hid] += dW1.reshape(-1)
+    grads[g.off_b1 : g.off_b1 + g.hid] += db1
+    grads[g.off_w2 : g.off_w2 + g.hid * g.cpad] += dW2.reshape(-1)
+    grads[g.off_b2 : g.off_b2 + g.cpad] += db2
+    grads[g.nparam] += loss
+
+
+def mlp_predict_reg_g(
+    g: Geometry,
+    X: torch.Tensor,  # [B][in_features] raw fp32
+    mean: torch.Tensor,
+    invstd: torch.Tensor,
+    W1bf: torch.Tensor,
+    W2bf: torch.Tensor,
+    master: torch.Tensor,
+    y_mean: torch.Tensor,   # [T]
+    y_scale: torch.Tensor,  # [T]
+) -> torch.Tensor:
+    """fp32 [B][T] in original target units: the standardized output
+    de-standardized in the epilogue, as mlp_predict_gen_kernel's
+    regression head does."""
+    _, b1, _, b2 = unpack_master_g(g, master)
+    T = g.classes
+    Xs = ((X - mean) * invstd).bfloat16().float()
+    if g.inp > g.in_features:  # zero-pad to the staged width
+        pad = torch.zeros(X.shape[0], g.inp - g.in_features, device=X.device)
+        Xs = torch.cat([Xs, pad], dim=1)
+    H = torch.relu(Xs @ W1bf.float() + b1)
+    z = H.bfloat16().float() @ W2bf.float() + b2
+    return z[:, :T] * y_scale + y_mean
 
 
 def adam_step_g(

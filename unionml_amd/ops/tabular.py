@@ -19,6 +19,9 @@ same class runs the pure-torch reference path
 (unionml_amd/ops/reference.py): one user-visible code path, two
 substrates.
 
+TabularMLPRegressor (bottom of this module) is the same machinery with a
+squared-error head over 1..32 continuous targets.
+
 Data parallel: under an active torch.distributed process group each
 rank trains its row shard and the flat gradient buffer is all-reduced
 on RCCL between the reduce-only step and the Adam kernel.
@@ -35,13 +38,18 @@ import torch
 from unionml_amd._logging import logger
 from unionml_amd.ops import hip_ext
 from unionml_amd.ops import reference as ref
-from unionml_amd.ops.reference import CPAD, HID, IN, Geometry
+from unionml_amd.ops.reference import (
+    CPAD, HEAD_CLASSIFIER, HEAD_REGRESSION, HID, IN, Geometry,
+)
 
 ADAM_BETA1, ADAM_BETA2, ADAM_EPS = 0.9, 0.999, 1e-8
 
 
 class TabularMLP:
     """Device-resident parameter/optimizer state + fused train/predict."""
+
+    #: the head the fused kernels end in; TabularMLPRegressor overrides it
+    HEAD = HEAD_CLASSIFIER
 
     def __init__(
         self,
@@ -51,7 +59,7 @@ class TabularMLP:
         device: Optional[str] = None,
         seed: int = 0,
     ):
-        self.g = Geometry(in_features, hidden, classes)
+        self.g = Geometry(in_features, hidden, classes, head=self.HEAD)
         if device is None:
             device = "cuda" if torch.cuda.is_available() else "cpu"
         self.device = torch.device(device)
@@ -218,10 +226,7 @@ class TabularMLP:
             )
             assert ok, "fused step slab capacity exceeded"
         else:
-            ok = ext.mlp_step_gen(
-                Xbf, y, g.hid, g.classes, rpw, self.wimg, self.master,
-                self.slabs, invBtot,
-            )
+            ok = self._gen_step_kernel(ext, Xbf, y, rpw, invBtot)
             assert ok, "fused step slab capacity exceeded"
             ext.reduce_adam_gen(
                 self.slabs, n_wg, g.inp, g.hid, g.cpad, self.master,
@@ -229,6 +234,24 @@ class TabularMLP:
                 loss_out, lr, ADAM_BETA1, ADAM_BETA2, ADAM_EPS,
                 wimg=self.wimg, grads_out=grads_out,
             )
+
+    def _gen_step_kernel(self, ext, Xbf, y, rpw: int, invBtot: float) -> bool:
+        """The generalized family's slab-producing step kernel, by head."""
+        g = self.g
+        return ext.mlp_step_gen(
+            Xbf, y, g.hid, g.classes, rpw, self.wimg, self.master,
+            self.slabs, invBtot,
+        )
+
+    def _ref_step(self, Xbf, y, invBtot: float):
+        """The CPU path's step (torch reference), by head."""
+        ref.mlp_step_g(
+            self.g, Xbf, y, self.W1bf, self.W2bf, self.master, self.grads, invBtot
+        )
+
+    def _prep_targets(self, y: torch.Tensor) -> torch.Tensor:
+        """Targets as the step kernels read them: int32 class labels."""
+        return y.to(self.device, torch.int32).contiguous()
 
     def _step_reduce(self, Xbf: torch.Tensor, y: torch.Tensor, invBtot: float, lr: float):
         """Reduce-only step: summed grads (+loss) into self.grads — the
@@ -258,7 +281,7 @@ class TabularMLP:
             self._step_reduce(Xbf, y, invBtot, lr)
         else:
             self.grads.zero_()
-            ref.mlp_step_g(g, Xbf, y, self.W1bf, self.W2bf, self.master, self.grads, invBtot)
+            self._ref_step(Xbf, y, invBtot)
         if allreduce:
             import torch.distributed as dist
 
@@ -342,7 +365,7 @@ class TabularMLP:
         holds a shard and gradients all-reduce over RCCL each step.
         """
         g = self.g
-        y = y.to(self.device, torch.int32).contiguous()
+        y = self._prep_targets(y)
         n = Xbf.shape[0]
         batches = [
             (off, min(batch_size, n - off)) for off in range(0, n, batch_size)
@@ -488,6 +511,9 @@ class TabularMLP:
 
     def load_state_dict(self, state: Dict[str, torch.Tensor]):
         g = self.g
+        head = state.get("head", HEAD_CLASSIFIER)
+        if head != g.head:
+            raise ValueError(f"state head {head!r} != model head {g.head!r}")
         if "geometry" in state:
             want = tuple(int(x) for x in state["geometry"])
             have = (g.in_features, g.hidden, g.classes)
@@ -513,3 +539,147 @@ class TabularMLP:
             self.t_dev.zero_()
         self._graph = self._graph_key = None
         self._build_wimg()
+
+
+class TabularMLPRegressor(TabularMLP):
+    """TabularMLP with a regression head: Linear -> ReLU -> Linear trained
+    on squared error over ``targets`` continuous outputs (1..32).
+
+    Everything but the head is TabularMLP's: the packed weight image, the
+    per-workgroup gradient slabs, the reduce+Adam kernel, hipGraph-captured
+    epochs, the RCCL all-reduce path and checkpointing. The step and the
+    predict kernels are the generalized family's regression instantiations
+    (tabular_gen.hip) at every shape, 64x32xT included; on the CPU the same
+    class runs ops/reference.py's ``mlp_step_reg_g``.
+
+    Targets are standardized per column like the features: the network
+    learns ``(Y - y_mean) * y_invstd`` and the predict kernel's epilogue
+    turns its output back into target units.
+    """
+
+    HEAD = HEAD_REGRESSION
+
+    def __init__(
+        self,
+        in_features: int,
+        hidden: int = 32,
+        targets: int = 1,
+        device: Optional[str] = None,
+        seed: int = 0,
+    ):
+        super().__init__(in_features, hidden, targets, device, seed)
+        T = self.g.classes
+        # target scaler: the identity until fit_target_standardizer
+        self.y_mean = torch.zeros(T, dtype=torch.float32, device=self.device)
+        self.y_invstd = torch.ones(T, dtype=torch.float32, device=self.device)
+        self.y_scale = torch.ones(T, dtype=torch.float32, device=self.device)
+
+    @property
+    def targets(self) -> int:
+        return self.g.classes
+
+    def _targets_2d(self, Y: torch.Tensor) -> torch.Tensor:
+        Y = torch.as_tensor(Y).to(self.device, torch.float32)
+        if Y.dim() == 1:
+            Y = Y.unsqueeze(1)
+        if Y.dim() != 2 or Y.shape[1] != self.g.classes:
+            raise ValueError(
+                f"targets must be [N][{self.g.classes}], got {tuple(Y.shape)}"
+            )
+        return Y.contiguous()
+
+    # -- target standardizer -----------------------------------------------------
+
+    def fit_target_standardizer(self, Y: torch.Tensor, eps: float = 1e-5):
+        """Column mean / inverse std of the targets (the feature
+        standardizer's kernel), and ``y_scale = 1 / y_invstd`` for the
+        predict epilogue."""
+        Y = self._targets_2d(Y)
+        if self.use_hip:
+            hip_ext().standardize_fit(Y, self.y_mean, self.y_invstd, eps)
+        else:
+            mean, invstd = ref.standardize_fit(Y, eps)
+            self.y_mean.copy_(mean)
+            self.y_invstd.copy_(invstd)
+        self.y_scale.copy_(1.0 / self.y_invstd)
+
+    def stage_targets(self, Y: torch.Tensor) -> torch.Tensor:
+        """Standardized fp32 targets, zero-padded to the kernel's
+        [N][cpad] layout (once per fit: plain torch ops, not the hot path)."""
+        g = self.g
+        Y = self._targets_2d(Y)
+        Yt = torch.zeros(Y.shape[0], g.cpad, dtype=torch.float32, device=self.device)
+        Yt[:, : g.classes] = (Y - self.y_mean) * self.y_invstd
+        return Yt
+
+    # -- training --------------------------------------------------------------
+
+    def _prep_targets(self, Yt: torch.Tensor) -> torch.Tensor:
+        Yt = Yt.to(self.device, torch.float32).contiguous()
+        if Yt.dim() != 2 or Yt.shape[1] != self.g.cpad:
+            raise ValueError(
+                f"Yt must be the staged [N][{self.g.cpad}] targets "
+                f"(stage_targets), got {tuple(Yt.shape)}"
+            )
+        return Yt
+
+    def _gen_step_kernel(self, ext, Xbf, Yt, rpw: int, invBtot: float) -> bool:
+        g = self.g
+        return ext.mlp_step_reg_gen(
+            Xbf, Yt, g.hid, g.classes, rpw, self.wimg, self.master,
+            self.slabs, invBtot,
+        )
+
+    def _ref_step(self, Xbf, Yt, invBtot: float):
+        ref.mlp_step_reg_g(
+            self.g, Xbf, Yt, self.W1bf, self.W2bf, self.master, self.grads, invBtot
+        )
+
+    def train_epochs(self, Xbf: torch.Tensor, Yt: torch.Tensor, *,
+                     engine: str = "auto", **kwargs) -> float:
+        """TabularMLP.train_epochs over staged targets ``Yt``
+        (stage_targets); returns the last step's loss, half the mean
+        squared error in standardized units summed over the targets. The
+        persistent engine exists for the digits classifier only."""
+        if engine == "persistent":
+            raise ValueError("engine='persistent' is a classifier engine")
+        return super().train_epochs(Xbf, Yt, engine=engine, **kwargs)
+
+    # -- inference -------------------------------------------------------------
+
+    def predict(self, X: torch.Tensor) -> torch.Tensor:
+        """fp32 [B][targets] in original target units."""
+        g = self.g
+        X = X.to(self.device, torch.float32).contiguous()
+        if self.use_hip:
+            out = torch.empty(X.shape[0], g.classes, dtype=torch.float32, device=self.device)
+            if X.shape[0]:
+                hip_ext().mlp_predict_reg_gen(
+                    X, g.inp, g.hid, g.classes, self.mean, self.invstd, self.wimg,
+                    self.master, self.y_mean, self.y_scale, out,
+                )
+            return out
+        return ref.mlp_predict_reg_g(
+            g, X, self.mean, self.invstd, self.W1bf, self.W2bf, self.master,
+            self.y_mean, self.y_scale,
+        )
+
+    # -- persistence -----------------------------------------------------------
+
+    def state_dict(self) -> Dict[str, torch.Tensor]:
+        """TabularMLP's state plus the head tag and the target scaler."""
+        state = super().state_dict()
+        state["head"] = HEAD_REGRESSION
+        state["y_mean"] = self.y_mean.cpu().clone()
+        state["y_invstd"] = self.y_invstd.cpu().clone()
+        return state
+
+    def load_state_dict(self, state: Dict[str, torch.Tensor]):
+        missing = [k for k in ("y_mean", "y_invstd") if k not in state]
+        if state.get("head") == HEAD_REGRESSION and missing:
+            # without its target scaler a regressor predicts in other units
+            raise ValueError(f"regression state lacks the target scaler: {missing}")
+        super().load_state_dict(state)   # raises on a classifier state
+        self.y_mean.copy_(state["y_mean"].to(self.device))
+        self.y_invstd.copy_(state["y_invstd"].to(self.device))
+        self.y_scale.copy_(1.0 / self.y_invstd)

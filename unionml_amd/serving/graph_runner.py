@@ -18,13 +18,18 @@ from unionml_amd.serving.batcher import bucket_for
 
 
 class TabularGraphRunner:
-    """Bucketed hipGraph replay around TabularMLP's fused predict kernel."""
+    """Bucketed hipGraph replay around TabularMLP's fused predict kernel.
+
+    A TabularMLPRegressor is served the same way: each bucket owns a
+    static fp32 ``[b][targets]`` output and calls return ``[n][targets]``
+    float32 instead of ``[n]`` int32 class ids."""
 
     def __init__(self, mlp, max_batch_size: int = 64, precapture: bool = True):
         from unionml_amd.ops.tabular import TabularMLP
 
         assert isinstance(mlp, TabularMLP)
         self.mlp = mlp
+        self.regression = mlp.g.head == "regression"
         self.max_batch = max_batch_size
         self.use_graphs = mlp.device.type == "cuda"
         self._buckets: Dict[int, tuple] = {}
@@ -49,11 +54,22 @@ class TabularGraphRunner:
         if entry is None:
             mlp = self.mlp
             x = torch.zeros(b, mlp.g.in_features, dtype=torch.float32, device=mlp.device)
-            preds = torch.zeros(b, dtype=torch.int32, device=mlp.device)
+            if self.regression:
+                preds = torch.zeros(
+                    b, mlp.g.classes, dtype=torch.float32, device=mlp.device
+                )
+            else:
+                preds = torch.zeros(b, dtype=torch.int32, device=mlp.device)
             ext = hip_ext(required=True)
 
             def fwd():
-                if mlp.use_spec:
+                if self.regression:
+                    ext.mlp_predict_reg_gen(
+                        x, mlp.g.inp, mlp.g.hid, mlp.g.classes, mlp.mean,
+                        mlp.invstd, mlp.wimg, mlp.master, mlp.y_mean,
+                        mlp.y_scale, preds,
+                    )
+                elif mlp.use_spec:
                     ext.mlp_predict(
                         x, mlp.mean, mlp.invstd, mlp.W1bf, mlp.W2bf,
                         mlp.master, preds, None,
@@ -82,7 +98,10 @@ class TabularGraphRunner:
         n = features.shape[0]
         if not self.use_graphs:
             return self.mlp.predict(features).cpu().numpy()
-        out = np.empty(n, dtype=np.int32)
+        if self.regression:
+            out = np.empty((n, self.mlp.g.classes), dtype=np.float32)
+        else:
+            out = np.empty(n, dtype=np.int32)
         off = 0
         while off < n:
             chunk = min(n - off, self.max_batch)
