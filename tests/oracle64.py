@@ -175,6 +175,54 @@ def adam64(master, grads_per_step, lr, b1, b2, eps):
     return out_p, out_m, out_v
 
 
+# Share of a tensor's entries adam_moments32 may exempt (a condition of the
+# tests that use it, not a measurement).
+MAX_MIDPOINT_SHARE = 1e-3
+
+_F32_MIN_NORMAL = 2.0 ** -126
+
+
+def _fma32(a, b, c):
+    """fp32 fma(a, b, c) of fp32 tensors, evaluated in fp64, and the entries
+    where that evaluation cannot be trusted to the last bit.
+
+    The product of two fp32 numbers is exact in fp64 (48 bits), so the only
+    fp64 rounding is the one of the sum; casting it to fp32 rounds a second
+    time. The two roundings differ from the single fp32 rounding of an fma
+    only when the fp64 sum sits exactly on the midpoint of two neighbouring
+    fp32 numbers: its 29 mantissa bits below fp32 precision are 1 followed
+    by 28 zeros. Those entries are flagged, and so is any non-zero sum below
+    the smallest normal fp32 number, where the midpoints lie elsewhere."""
+    s = a.to(F64) * b.to(F64) + c.to(F64)
+    low = s.view(torch.int64) & 0x1FFFFFFF
+    exempt = (low == 0x10000000) | ((s != 0) & (s.abs() < _F32_MIN_NORMAL))
+    return s.float(), exempt
+
+
+def adam_moments32(m, v, gr, b1: float, b2: float):
+    """One step of the moments as adam_update (tabular_common.h) writes them,
+    from fp32 ``m``, ``v`` and gradient ``gr``; ``b1``/``b2`` are the betas
+    already rounded to fp32. With rn() one fp32 rounding:
+
+        m' = fma(1-b1, g, rn(b1*m))
+        v' = fma(g, rn((1-b2)*g), rn(b2*v))
+
+    Evaluated in fp64, where every fp32 x fp32 product is exact and rn() is
+    the cast to fp32 (1-b is exact in fp64 too, so its cast is the fp32
+    subtraction). Returns (m', v', exempt_m, exempt_v): the bool masks mark
+    the entries whose fma may be double-rounded here (see _fma32)."""
+    assert m.dtype == v.dtype == gr.dtype == torch.float32
+    t = lambda x: torch.tensor(x, dtype=F64)   # noqa: E731
+    rn = lambda x: x.float()                   # noqa: E731
+    omb1, omb2 = rn(1.0 - t(b1)), rn(1.0 - t(b2))
+    bm = rn(t(b1) * m.to(F64))
+    bv = rn(t(b2) * v.to(F64))
+    gs = rn(omb2.to(F64) * gr.to(F64))
+    m_new, ex_m = _fma32(omb1, gr, bm)
+    v_new, ex_v = _fma32(gr, gs, bv)
+    return m_new, v_new, ex_m, ex_v
+
+
 def standardize64(X, eps: float = 1e-5):
     """Two-pass column statistics in fp64: (mean, invstd, var)."""
     Xd = X.to(F64)
@@ -281,7 +329,9 @@ PRED_INSTANTIATIONS = [
     ((256, 32, 32), (30, 256, 20)),
 ]
 
-SPEC_STEP_BATCHES = (1, 127, 129, 273)
+# ... and the benchmark's grids: 16 workgroups with a tail of one row, and 65
+# (past the 64 lanes of one tag-poll round, last workgroup's stripe empty)
+SPEC_STEP_BATCHES = (1, 127, 129, 273, 1921, 8197)
 SPEC_RT = 128
 
 DEFAULT_SEED = 5
@@ -340,8 +390,10 @@ def predict_cases():
     return out
 
 
-# smallest geometry end to end: (shape, B)
-E2E_CASES = [((1, 1, 2), 1), ((1, 1, 2), 65), ((33, 250, 3), 1), ((33, 250, 3), 65)]
+# smallest geometry end to end, and one full-mode step of the specialized
+# kernel on 16 workgroups: (shape, B)
+E2E_CASES = [((1, 1, 2), 1), ((1, 1, 2), 65), ((33, 250, 3), 1), ((33, 250, 3), 65),
+             ((64, 32, 10), 1921)]
 
 
 def check_instantiation(inst, shape):
@@ -351,6 +403,14 @@ def check_instantiation(inst, shape):
 
 
 # Adam bound pieces ----------------------------------------------------------
+
+
+# the moments-against-the-written-formula tests (adam_moments32): kernels and
+# geometries of test_gpu_oracle.py's Adam tests, their gradient seed, 4 steps
+ADAM_KERNELS = [("adam_step", (64, 32, 10)), ("adam_step_gen", (100, 50, 7)),
+                ("reduce_adam_gen", (100, 50, 7))]
+ADAM_MOMENT_STEPS = 4
+ADAM_GRAD_SEED = 17
 
 
 def moment_envelopes(grads_per_step, b1, b2):

@@ -3,6 +3,8 @@ the GPU oracle tests run: the oracle against torch.autograd, and, for every
 case, the conditions the kernel-vs-oracle bounds rest on, measured on the
 bf16-mirroring reference (never on a kernel)."""
 
+from fractions import Fraction
+
 import pytest
 import torch
 
@@ -166,3 +168,101 @@ def test_standardize64_two_pass():
     want = centered.var(unbiased=False)
     assert abs(float(var[0]) - float(want)) <= 1e-12 * float(want)
     assert abs(float(invstd[1]) - 1e-5 ** -0.5) <= 1e-12 * 1e-5 ** -0.5
+
+
+# ---------------------------------------------------------------------------
+# the pinned moment formulas (adam_moments32) against exact rationals
+# ---------------------------------------------------------------------------
+
+
+def _rn32(x: Fraction) -> float:
+    """x rounded to the nearest fp32 number, ties to even, as a float
+    (exact: every fp32 number is a float). Subnormals included."""
+    if x == 0:
+        return 0.0
+    sign, x = (-1.0, -x) if x < 0 else (1.0, x)
+    e = x.numerator.bit_length() - x.denominator.bit_length()
+    if Fraction(2) ** e > x:
+        e -= 1                      # now 2^e <= x < 2^(e+1)
+    ulp = Fraction(2) ** (max(e, -126) - 23)
+    q = x / ulp
+    n = q.numerator // q.denominator
+    r = q - n
+    if r > Fraction(1, 2) or (r == Fraction(1, 2) and n % 2 == 1):
+        n += 1
+    return sign * float(n * ulp)
+
+
+def test_rn32_rounds_to_nearest_even():
+    one, ulp = Fraction(1), Fraction(2) ** -23
+    assert _rn32(one + ulp / 2) == 1.0                        # tie -> even
+    assert _rn32(one + ulp + ulp / 2) == 1.0 + 2.0 ** -22     # tie -> even, upward
+    assert _rn32(one + ulp / 2 + Fraction(2) ** -80) == 1.0 + 2.0 ** -23
+    assert _rn32(-(one + ulp / 2 - Fraction(2) ** -80)) == -1.0
+    assert _rn32(Fraction(2) ** -149 * 3 / 2) == 2.0 ** -148  # subnormal tie -> even
+    assert _rn32(Fraction(2) - Fraction(2) ** -30) == 2.0     # carries into the next binade
+    for x in (0.1, -3.75e-7, 12345.678):
+        assert _rn32(Fraction(x)) == float(torch.tensor(x, dtype=torch.float64).float())
+
+
+def _moments_exact(m, v, gr, b1, b2):
+    """adam_moments32's formulas, entry by entry, in exact rationals with one
+    explicit rounding per rn() and per fma"""
+    B1, B2 = Fraction(b1), Fraction(b2)
+    omb1, omb2 = Fraction(_rn32(1 - B1)), Fraction(_rn32(1 - B2))
+    m_new, v_new = [], []
+    for mi, vi, gi in zip(m.tolist(), v.tolist(), gr.tolist()):
+        mi, vi, gi = Fraction(mi), Fraction(vi), Fraction(gi)
+        bm, bv = Fraction(_rn32(B1 * mi)), Fraction(_rn32(B2 * vi))
+        gs = Fraction(_rn32(omb2 * gi))
+        m_new.append(_rn32(omb1 * gi + bm))
+        v_new.append(_rn32(gi * gs + bv))
+    return (torch.tensor(m_new, dtype=torch.float64).float(),
+            torch.tensor(v_new, dtype=torch.float64).float())
+
+
+@pytest.mark.parametrize("betas", [(0.9, 0.999), (0.8, 0.95)], ids=["default", "b0.8-0.95"])
+@pytest.mark.parametrize("shape", sorted({s for _, s in o64.ADAM_KERNELS}),
+                         ids=o64.shape_id)
+def test_adam_moments32_matches_exact_rationals(shape, betas):
+    """The fp64 evaluation of the pinned moment formulas equals their exact
+    rational evaluation on every entry it does not exempt, over the
+    gradients test_gpu_oracle.py draws, and it exempts at most
+    MAX_MIDPOINT_SHARE of a tensor. An fma whose double rounding really
+    goes wrong must be flagged; a made-up one shows the flag works."""
+    n = Geometry(*shape).nparam
+    grads, _ = o64.adam_gradients(n, o64.ADAM_MOMENT_STEPS, seed=o64.ADAM_GRAD_SEED)
+    b1 = float(torch.tensor(betas[0]).float())
+    b2 = float(torch.tensor(betas[1]).float())
+    m, v = torch.zeros(n), torch.zeros(n)
+    exempted = 0
+    for t, gr in enumerate(grads, start=1):
+        m_new, v_new, ex_m, ex_v = o64.adam_moments32(m, v, gr, b1, b2)
+        m_x, v_x = _moments_exact(m, v, gr, b1, b2)
+        for name, got, want, ex in (("m", m_new, m_x, ex_m), ("v", v_new, v_x, ex_v)):
+            share = float(ex.double().mean())
+            assert share <= o64.MAX_MIDPOINT_SHARE, f"{name} t={t}: exempts {share:.2e}"
+            assert torch.equal(got[~ex], want[~ex]), f"{name} t={t}"
+            exempted += int(ex.sum())
+        m, v = m_x, v_x
+    print(f"adam_moments32 {o64.shape_id(shape)} betas={betas}: {exempted} entries exempted "
+          f"of {2 * n * len(grads)}")
+
+
+def test_fma32_flags_a_double_rounding():
+    """fma(a, b, c) with a*b = 2^-24 - 2^-70 and c = 1 + 2^-23: the exact sum
+    lies just below the midpoint of 1 + 2^-23 and 1 + 2^-22 and rounds to the
+    former in one step; fp64 first rounds it ONTO the midpoint, and the tie
+    then goes to the even neighbour 1 + 2^-22. That entry must be flagged
+    (and really is wrong); a true tie is flagged too, harmlessly; a sum away
+    from every midpoint is not."""
+    h = 2.0 ** -12
+    a = torch.tensor([h * (1 + 2.0 ** -23), h, 0.25], dtype=torch.float32)
+    b = torch.tensor([h * (1 - 2.0 ** -23), h, 0.5], dtype=torch.float32)
+    c = torch.tensor([1 + 2.0 ** -23, 1.0, 1.0], dtype=torch.float32)
+    got, ex = o64._fma32(a, b, c)
+    assert ex.tolist() == [True, True, False]
+    exact = [_rn32(Fraction(x) * Fraction(y) + Fraction(z))
+             for x, y, z in zip(a.tolist(), b.tolist(), c.tolist())]
+    assert exact == [1 + 2.0 ** -23, 1.0, 1.125]
+    assert got.tolist() == [1 + 2.0 ** -22, 1.0, 1.125]   # entry 0: double-rounded

@@ -115,9 +115,16 @@ __device__ __forceinline__ float group_max(float x) {
 }
 
 // ---------------------------------------------------------------------------
-// Adam. Every kernel that steps the optimizer calls adam_update, so the
-// expression order (and with it the last bit of every weight) is the same
-// on every training path.
+// Adam. Every kernel that steps the optimizer calls adam_update. Sharing the
+// source expression is not enough to share its bits: left to itself the
+// compiler contracts the inlined a*b + c*d sums into a different fma at
+// different call sites (adam_step_kernel and adam_step_gen_kernel rounded
+// the moments differently from the three fused kernels). So adam_update
+// leaves the compiler no such choice (see below); each call site then
+// compiles to the same arithmetic and the last bit of m, v and every
+// weight is the same on every training path.
+// (adam_bias_corr is separate: the persistent kernel keeps its own
+// running-product beta^t, docs/kernels.md "Determinism".)
 // ---------------------------------------------------------------------------
 
 // bias-correction factor 1/(1 - beta^t), from the power beta^t
@@ -132,12 +139,30 @@ __device__ __forceinline__ void adam_bias_corr(float beta1, float beta2, float t
   corr2 = adam_corr(__powf(beta2, t));
 }
 
-// p/m/v hold the old values on entry and the new ones on return
+// p/m/v hold the old values on entry and the new ones on return. With rn()
+// one fp32 rounding:
+//   m' = fma(1-beta1, g, rn(beta1*m))
+//   v' = fma(g, rn((1-beta2)*g), rn(beta2*v))
+//   p' = fma(-rn(lr*rn(m'*corr1)), rcp(sqrt(rn(v'*corr2)) + eps), p)
+// The three products that feed an fma are rounded on their own (contraction
+// off in their block) and the two moment fmas are explicit, so no call site
+// can pick another pairing. The last line has a single product under its
+// subtraction, hence a single way to contract it. The statements keep the
+// evaluation order of the plain expression they replace, so the three
+// fused kernels compile to the instructions they had before.
 __device__ __forceinline__ void adam_update(float& p, float& m, float& v, float g,
                                             float lr, float beta1, float beta2,
                                             float eps, float corr1, float corr2) {
-  const float mi = beta1 * m + (1.f - beta1) * g;
-  const float vi = beta2 * v + (1.f - beta2) * g * g;
+  const float omb1 = 1.f - beta1, omb2 = 1.f - beta2;
+  float bm, bv, gs;
+  {
+    #pragma clang fp contract(off)
+    bm = beta1 * m;
+    bv = beta2 * v;
+    gs = omb2 * g;
+  }
+  const float mi = __builtin_fmaf(omb1, g, bm);
+  const float vi = __builtin_fmaf(g, gs, bv);
   m = mi;
   v = vi;
   p = p - lr * (mi * corr1) * fast_rcp(sqrtf(vi * corr2) + eps);

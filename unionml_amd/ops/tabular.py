@@ -159,6 +159,8 @@ class TabularMLP:
                 n_wg, self.g.slab_stride, dtype=torch.float32, device=self.device
             )
             self.counter = torch.zeros(1, dtype=torch.uint32, device=self.device)
+            # a captured epoch holds the old slabs' and counter's addresses
+            self._graph = self._graph_key = None
 
     # -- views ----------------------------------------------------------------
 
@@ -344,7 +346,9 @@ class TabularMLP:
                     Xbf[off : off + bs], y[off : off + bs], 1.0 / bs, lr, loss_out
                 )
 
-        key = ("fused", len(batches), lr, Xbf.data_ptr(), y.data_ptr())
+        # the capture bakes in every batch's offset, row count and 1/bs:
+        # the key is the batch list itself, not its length
+        key = ("fused", tuple(batches), lr, Xbf.data_ptr(), y.data_ptr())
         return self._run_epochs(run_epoch, epochs, key, use_graph)
 
     def train_epochs(
