@@ -115,6 +115,47 @@ __device__ __forceinline__ float group_max(float x) {
 }
 
 // ---------------------------------------------------------------------------
+// Accesses to memory that another workgroup of the SAME launch writes or
+// reads (the fused step's gradient slabs and their epoch tags). Every one is
+// a global-address-space access carrying sc1: an sc1 store is written
+// through, so the bytes leave the XCD's L2 as they are stored and no agent
+// release has to write them back; an sc1 load bypasses the CU's L1, the one
+// cache another CU's stores never refresh, so no agent acquire has to
+// invalidate it. Both hold only if EVERY access to such a byte goes through
+// these helpers (guide §6 G16, Rule); none of them waits or orders anything.
+// ---------------------------------------------------------------------------
+
+typedef __attribute__((address_space(1))) float xwg_f32;
+typedef __attribute__((address_space(1))) unsigned xwg_u32;
+
+// 4-byte store / load (global_store_dword / global_load_dword ... sc1)
+__device__ __forceinline__ void xwg_store(float* p, float x) {
+  __hip_atomic_store((xwg_f32*)p, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void xwg_store(unsigned* p, unsigned x) {
+  __hip_atomic_store((xwg_u32*)p, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ float xwg_load(const float* p) {
+  return __hip_atomic_load((const xwg_f32*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ unsigned xwg_load(const unsigned* p) {
+  return __hip_atomic_load((const xwg_u32*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// 16-byte store of the four consecutive floats base[i .. i+3] as ONE
+// buffer_store_dwordx4 ... sc1 (aux bit 4); base + i 16-byte aligned. There
+// is no 16-byte atomic to ask for, hence the raw buffer form. The descriptor
+// lives in scalar registers, so base and n (the floats it spans) must be
+// uniform over the wave and only i may differ from lane to lane; a store
+// that would reach past base[n) is dropped by the hardware.
+__device__ __forceinline__ void xwg_store4(float* base, int n, int i, f32x4 x) {
+  typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
+  const __amdgpu_buffer_rsrc_t rsrc =       // raw, stride 0, 32-bit data format
+      __builtin_amdgcn_make_buffer_rsrc(base, 0, n * 4, 0x00020000);
+  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, x), rsrc, i * 4, 0, 16);
+}
+
+// ---------------------------------------------------------------------------
 // Adam. Every kernel that steps the optimizer calls adam_update. Sharing the
 // source expression is not enough to share its bits: left to itself the
 // compiler contracts the inlined a*b + c*d sums into a different fma at

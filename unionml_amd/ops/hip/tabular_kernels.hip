@@ -627,12 +627,36 @@ mlp_step_kernel(const u16* __restrict__ Xbf, const int* __restrict__ y, int B,
 
 // ---------------------------------------------------------------------------
 // fully-fused step kernel: fwd + bwd + cross-WG grad reduction + Adam in ONE
-// launch. Each workgroup writes its complete partial-grad slab (plain
-// stores), publishes it with the agent-scope release + ticket-counter
-// hand-off of guide §6 G16 (split-K seam form), and the LAST-arriving
-// workgroup acquires, reduces the slabs and applies Adam. The DP path needs
-// the summed grads for RCCL: it runs this kernel in reduce-only mode
-// (grads_out) and applies Adam afterwards with adam_step_kernel.
+// launch. Each workgroup writes its complete partial-grad slab, signals it
+// with the slab's epoch tag, waits until every slab of the launch carries
+// this launch's tag, then sums ITS stripe of the parameters over all slabs
+// and applies Adam to that stripe. The DP path needs the summed grads for
+// RCCL: it runs this kernel in reduce-only mode (grads_out) and applies Adam
+// afterwards with adam_step_kernel.
+//
+// The hand-off between the workgroups uses NO agent-scope fence (neither
+// buffer_wbl2 nor buffer_inv): it is the write-through form of guide §6 G16,
+// first row of the table of hand-offs measured with sc1 loads in place of
+// the acquire (one lane of each storing workgroup signals with an sc1 flag
+// store for all that workgroup's stores; the consumer polls the flags with
+// sc1 loads; the other waves load after a workgroup barrier the polling wave
+// joins; hipMalloc memory; one workgroup per CU; 4- and 16-byte stores,
+// 4-byte loads). What makes it valid, and has to stay true after any edit:
+//   (1) every store to slab memory is an sc1 store (xwg_store/xwg_store4,
+//       tabular_common.h): written through, nothing left for a release;
+//   (2) every storing wave drains its stores (s_waitcnt vmcnt(0)) and then
+//       reaches the workgroup barrier BEFORE lane 0 stores the tag;
+//   (3) the tag is stored and polled sc1;
+//   (4) every load of a slab byte is an sc1 load (xwg_load) that sits
+//       behind the poll and the barrier after it, and every OTHER load of the
+//       kernel reads bytes no other workgroup writes in this launch: X and
+//       the labels are never written; wimg / W1bf / W2bf and the biases in
+//       master are written only in the Adam phase, which no workgroup enters
+//       before ALL have published, i.e. after all have finished their
+//       prologue loads; the prefetched master/m/v stripe is written only by
+//       the workgroup that reads it; counter and t_dev are written by
+//       workgroup 0 as its last act, after every workgroup has published and
+//       so has read them.
 // ---------------------------------------------------------------------------
 
 extern "C" __global__ void __launch_bounds__(BLOCK)
@@ -713,33 +737,40 @@ mlp_step_fused_kernel(const u16* __restrict__ Xbf, const int* __restrict__ y,
   chunk_fwd_bwd(L, L.b1s, L.b2s, chunk_label(xr), xr.valid, invBtot, acc);
 #endif
 
-  // ---- write this WG's complete partial slab (plain stores, no atomics) ----
+  // ---- write this WG's complete partial slab: write-through (sc1) stores,
+  // no atomics. Condition (1) of the header: EVERY slab word goes out through
+  // xwg_store / xwg_store4. ---------------------------------------------------
   float* slab = slabs + (long long)blockIdx.x * SLAB;
   {
+    // the wave's dW1^T tile holds, per lane, the four consecutive floats
+    // h = ht*16 + lg*4 + r of row `in`: ONE 16-byte sc1 store per lane (a
+    // bulk publish re-issued as narrow sc1 stores costs one fabric write
+    // per store, G16 pitfall 7). 16-byte aligned: in * HID + ht*16 + lg*4
+    // is a multiple of 4 floats, and so are OFF_W1 and SLAB.
+    static_assert(OFF_W1 % 4 == 0 && HID % 4 == 0 && SLAB % 4 == 0, "16-B dW1 stores");
     const int ht = wave & 1, it = wave >> 1;
-    #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int h = ht * 16 + lg * 4 + r;
-      const int in = it * 16 + lr_;
-      slab[OFF_W1 + in * HID + h] = acc.dW1[r];
-    }
+    const int in = it * 16 + lr_;
+    xwg_store4(slab, SLAB, OFF_W1 + in * HID + ht * 16 + lg * 4, acc.dW1);
   }
   if (wave < 2) {
+    // dW2's registers are CPAD floats apart: the epilogue's natural 4-byte
+    // sc1 stores (each store instruction still fills whole 64-byte rows)
     #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int h = wave * 16 + lg * 4 + r;
-      slab[OFF_W2 + h * CPAD + lr_] = acc.dW2[r];
+      xwg_store(&slab[OFF_W2 + h * CPAD + lr_], acc.dW2[r]);
     }
   }
-  if (tid < HID) slab[OFF_B1 + tid] = L.db1[tid];
-  else if (tid < HID + CPAD) slab[OFF_B2 + tid - HID] = L.db2[tid - HID];
-  else if (tid == HID + CPAD) slab[OFF_LOSS] = L.loss[0];
+  if (tid < HID) xwg_store(&slab[OFF_B1 + tid], L.db1[tid]);
+  else if (tid < HID + CPAD) xwg_store(&slab[OFF_B2 + tid - HID], L.db2[tid - HID]);
+  else if (tid == HID + CPAD) xwg_store(&slab[OFF_LOSS], L.loss[0]);
 
-  // ---- publish + all-WG barrier (guide §6 G16: R1 release + per-slab epoch
-  // tag, R2 data-is-the-flag poll). The tag is this step's epoch t_pre+1 —
-  // unique per launch (exactly one WG advances t_dev per launch), so the
-  // scheme is robust to any grid size, graph replay, and engine mixing;
-  // no counter, no reset. ----------------------------------------------------
+  // ---- signal + all-WG barrier (guide §6 G16, write-through form: sc1
+  // payload, every storing wave drains, ONE lane stores the per-slab epoch
+  // tag sc1). The tag is this launch's epoch counter_pre+1 — unique per
+  // launch (exactly one WG advances the counter per launch), so the scheme
+  // is robust to any grid size, graph replay, and engine mixing; no
+  // reset. --------------------------------------------------------------------
   const unsigned epoch = lossu[2] + 1u;
   // Adam-state prefetch scratch (loads issued during the sweep below);
   // the chunk arrays are dead from here on — reuse Xs
@@ -749,21 +780,24 @@ mlp_step_fused_kernel(const u16* __restrict__ Xbf, const int* __restrict__ y,
   const bool use_pre =
       (grads_out == nullptr) && (3 * span_pre * 4 <= ROWS * XS * 2);
 #ifndef PROBE_SKIP_HANDSHAKE
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // EVERY storing wave drains
+  // Condition (2): EVERY storing wave waits until its write-through stores
+  // have completed (inline asm, so no compiler pass can drop the wait), and
+  // only behind the barrier, i.e. behind every wave's wait, does lane 0
+  // signal for the whole workgroup. No release fence: nothing of the slab is
+  // left dirty in L2 for one to write back.
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  if (tid == 0) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // keep: ROCm may drop it
-    __hip_atomic_store((unsigned*)(slab + NPARAM + 1), epoch, __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT);
-  }
-  __syncthreads();                                   // tag stored before polls
+  if (tid == 0) xwg_store((unsigned*)(slab + NPARAM + 1), epoch);   // (3)
+  // No barrier between the tag store and the polls: nothing reads what the
+  // tag store orders. Lane 0 sits in the polling wave itself, the other
+  // waves only prefetch their own Adam stripe until the barrier behind the
+  // poll, and another workgroup sees the tag whenever it arrives.
 
   // prefetch this WG's Adam-state stripe (master/m/v) into LDS WHILE the
   // sweep waits — these are only ever written by this same WG's stripe
-  // in the reduce phase, so reading them before the acquire is safe, and
-  // it pulls an otherwise-cold post-invalidate HBM round trip out of the
-  // reduce chain.
+  // in the reduce phase, so plain loads ahead of the poll are safe
+  // (condition (4)), and it pulls an HBM round trip out of the reduce
+  // chain.
   if (use_pre) {
     const int hi_pre = min(lo_pre + span_pre, NPARAM);
     for (int i = lo_pre + tid; i < hi_pre; i += BLOCK) {
@@ -784,9 +818,8 @@ mlp_step_fused_kernel(const u16* __restrict__ Xbf, const int* __restrict__ y,
     bool ok = true;
     for (int w = l; w < n_wg; w += 64) {
       for (;;) {
-        const unsigned tag = __hip_atomic_load(
-            (const unsigned*)(slabs + (long long)w * SLAB + NPARAM + 1),
-            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const unsigned tag = xwg_load(
+            (const unsigned*)(slabs + (long long)w * SLAB + NPARAM + 1));
         if (tag == epoch) break;
         __builtin_amdgcn_s_sleep(2);
         if (++spins > 100000000u) { ok = false; break; }
@@ -794,11 +827,15 @@ mlp_step_fused_kernel(const u16* __restrict__ Xbf, const int* __restrict__ y,
       if (!ok) break;
     }
     const unsigned long long bad = __ballot(!ok);
-    if (l == 0) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      lossu[1] = bad ? 1u : 0u;
-    }
+    // No agent acquire: every slab load below is an sc1 load, which does
+    // not look into this CU's L1, so there is no stale line to invalidate
+    // (condition (4)). The wavefront-scope fence emits no instruction; it
+    // keeps the compiler from moving those loads above the poll.
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if (l == 0) lossu[1] = bad ? 1u : 0u;
   }
+  // the polling wave joins this barrier only after its poll has matched:
+  // the other waves' slab loads all sit behind it
   __syncthreads();
   if (lossu[1] != 0u) {             // timed out: poison the loss, keep going
     if (tid == 0 && blockIdx.x == 0) *loss_out = __builtin_nanf("");
@@ -821,20 +858,46 @@ mlp_step_fused_kernel(const u16* __restrict__ Xbf, const int* __restrict__ y,
   const int lo = blockIdx.x * span;
   const int hi = min(lo + span, NPARAM + 1);
   for (int i = lo + tid; i < hi; i += BLOCK) {
-    float g0 = 0.f, g1 = 0.f, g2 = 0.f, g3 = 0.f;
-    float g4 = 0.f, g5 = 0.f, g6 = 0.f, g7 = 0.f;
+    // Eight chains: chain k sums the slabs w = k, k+8, k+16, ... in that
+    // order; the remainder (n_wg % 8 slabs) goes into chain 0; then the
+    // chains are folded pairwise. That order is pinned bit for bit. What is
+    // free is how many loads are in flight: each batch below issues ALL its
+    // loads before its first add (a batch is one memory round trip, and a
+    // written-through slab word is in no L2), 16 slabs at a time, then 8,
+    // then the remainder's up to 7 in one batch as well. The remainder
+    // loads unconditionally, past the grid's end the last slab once more,
+    // and only the ADD is predicated (adding a zero instead could turn a
+    // -0 sum into +0). Every slab word through xwg_load (sc1, past the
+    // L1): condition (4).
+    float gc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     int w = 0;
-    for (; w + 8 <= n_wg; w += 8) {      // 8 independent load chains
-      g0 += slabs[(long long)w * SLAB + i];
-      g1 += slabs[(long long)(w + 1) * SLAB + i];
-      g2 += slabs[(long long)(w + 2) * SLAB + i];
-      g3 += slabs[(long long)(w + 3) * SLAB + i];
-      g4 += slabs[(long long)(w + 4) * SLAB + i];
-      g5 += slabs[(long long)(w + 5) * SLAB + i];
-      g6 += slabs[(long long)(w + 6) * SLAB + i];
-      g7 += slabs[(long long)(w + 7) * SLAB + i];
+    for (; w + 16 <= n_wg; w += 16) {
+      float a[16];
+      #pragma unroll
+      for (int k = 0; k < 16; ++k) a[k] = xwg_load(&slabs[(long long)(w + k) * SLAB + i]);
+      #pragma unroll
+      for (int k = 0; k < 16; ++k) gc[k & 7] += a[k];
     }
-    for (; w < n_wg; ++w) g0 += slabs[(long long)w * SLAB + i];
+    for (; w + 8 <= n_wg; w += 8) {
+      float a[8];
+      #pragma unroll
+      for (int k = 0; k < 8; ++k) a[k] = xwg_load(&slabs[(long long)(w + k) * SLAB + i]);
+      #pragma unroll
+      for (int k = 0; k < 8; ++k) gc[k] += a[k];
+    }
+    if (w < n_wg) {
+      float a[7];
+      #pragma unroll
+      for (int k = 0; k < 7; ++k) {
+        a[k] = xwg_load(&slabs[(long long)min(w + k, n_wg - 1) * SLAB + i]);
+      }
+      #pragma unroll
+      for (int k = 0; k < 7; ++k) {
+        if (w + k < n_wg) gc[0] += a[k];
+      }
+    }
+    const float g0 = gc[0], g1 = gc[1], g2 = gc[2], g3 = gc[3];
+    const float g4 = gc[4], g5 = gc[5], g6 = gc[6], g7 = gc[7];
     const float g = ((g0 + g1) + (g2 + g3)) + ((g4 + g5) + (g6 + g7));
     if (grads_out) {            // reduce-only: hand the summed grads (+loss
       grads_out[i] = g;         // at NPARAM) to the RCCL all-reduce
