@@ -2,8 +2,11 @@
 // to excise a phase and difference the step time (timing only — skipped
 // phases leave garbage math, never use for numerics).
 //
-//   hipcc --offload-arch=gfx950 -O3 -o benchmarks/probe_base.bin benchmarks/probe_floor.hip
+//   hipcc --offload-arch=gfx950 -O3 -mllvm -amdgpu-kernarg-preload-count=16 \
+//         -o benchmarks/probe_base.bin benchmarks/probe_floor.hip
 //   hipcc ... -DPROBE_SKIP_FWDBWD -o benchmarks/probe_nofwd.bin ...
+// (the -mllvm flag is the extension's, setup.py: without it the probe times
+// a kernel that fetches its first arguments by a scalar load)
 //
 #include "../unionml_amd/ops/hip/tabular_kernels.hip"
 

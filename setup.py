@@ -28,7 +28,12 @@ ext = CUDAExtension(
     ],
     extra_compile_args={
         "cxx": ["-O3", "-std=c++17"],
-        "nvcc": ["-O3", "-std=c++17", "--offload-arch=gfx950"],
+        # kernel-argument preload: the first 16 dwords of a kernel's
+        # arguments arrive in scalar registers at wave start instead of by a
+        # scalar load (each kernel keeps a compatibility entry that loads
+        # them). mlp_step_fused_kernel orders its parameters for it.
+        "nvcc": ["-O3", "-std=c++17", "--offload-arch=gfx950",
+                 "-mllvm", "-amdgpu-kernarg-preload-count=16"],
     },
 )
 

@@ -276,6 +276,22 @@ __device__ __forceinline__ void head_logits(float (&logit)[NCT][4],
   }
 }
 
+// the same for one tile whose bias array is padded to the tile (16 floats):
+// the caller reads its lane's four values b2[lg*4 .. lg*4+3] as ONE 16-byte
+// read, unconditionally and as early as it likes, and the pad is masked
+// here. (The form above reads each b2[c] under its c < cls branch: four
+// serial LDS round trips between the fwd2 MFMA and the row max.) Same adds,
+// same select, same bits.
+__device__ __forceinline__ void head_logits_padded(float (&logit)[1][4],
+                                                   const f32x4 (&acc)[1],
+                                                   f32x4 b2v, int cls, int lg) {
+  #pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int c = lg * 4 + r;
+    logit[0][r] = (c < cls) ? acc[0][r] + b2v[r] : -1e30f;
+  }
+}
+
 // row max: fold the register-resident tile axis, then the 4 lane groups
 template <int NCT>
 __device__ __forceinline__ float head_row_max(const float (&logit)[NCT][4]) {

@@ -295,6 +295,19 @@ __device__ __forceinline__ float issue_biases(const float* __restrict__ b1,
   return *p;
 }
 
+// one word that every thread wants, as a VECTOR load of a uniform address
+// (global_load_dword, no cache-policy bit). A plain read of a uniform
+// address compiles to a scalar load, which sits on the scalar counter with
+// the LDS traffic and gets a wait of its own; a relaxed wavefront-scope
+// atomic load is never made scalar, costs nothing more than a plain load,
+// and is counted with the other prologue loads.
+template <typename T>
+__device__ __forceinline__ T uniform_load(const T* p) {
+  static_assert(sizeof(T) == 4, "one dword");
+  typedef __attribute__((address_space(1))) const T gT;
+  return __hip_atomic_load((gT*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+}
+
 __device__ __forceinline__ void store_biases(float b, const Lds& L) {
   const int tid = threadIdx.x;
   if (tid < HID) L.b1s[tid] = b;
@@ -386,12 +399,21 @@ __device__ __forceinline__ void store_x_chunk(const XChunkRegs& R, const Lds& L)
   }
 }
 
-// zero DLs K-pad cols [CPAD,32) once per launch (never rewritten)
+// zero DLs K-pad cols [CPAD,32) once per launch (never rewritten): 32 bytes
+// per row, as two 16-byte stores; thread t takes half t&1 of row t>>1
 __device__ __forceinline__ void zero_dl_pad(const Lds& L) {
-  for (int i = threadIdx.x; i < ROWS * CPAD; i += BLOCK) {
-    const int r = i / CPAD, c = CPAD + (i % CPAD);
-    L.DLs[r][c] = 0;
-  }
+  static_assert(2 * ROWS <= BLOCK && CPAD == 16 && (HS * 2) % 16 == 0, "one b128 store per thread");
+  const int t = threadIdx.x;
+  if (t < 2 * ROWS) *(bf16x8*)&L.DLs[t >> 1][CPAD + (t & 1) * 8] = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
+}
+
+// four consecutive bf16 of one row-major LDS image row (8-byte aligned: the
+// column is a multiple of 4 and the row strides are multiples of 16 bytes)
+// as ONE 8-byte store, in place of four 2-byte ones
+typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
+__device__ __forceinline__ void store_bf16x4(u16* p, const u16 (&x)[4]) {
+  *(u32x2*)p = (u32x2){(unsigned)x[0] | ((unsigned)x[1] << 16),
+                       (unsigned)x[2] | ((unsigned)x[3] << 16)};
 }
 
 struct ChunkAcc {
@@ -399,40 +421,88 @@ struct ChunkAcc {
   f32x4 dW2;        // waves 0-1: dW2 tile (h-tile = wave)
 };
 
-// one 128-row chunk: fwd + bwd, accumulating weight grads in acc_io and
-// bias grads / loss in LDS. b1/b2 point at fp32 biases (any addr space).
+// one 128-row chunk: fwd + bwd, accumulating weight grads in acc_io. b1/b2
+// point at fp32 biases in LDS, 16-byte aligned, b2 padded to CPAD floats.
 // label/valid describe this thread's softmax row (wrow + lr) and come from
 // issue_x_chunk: the label was loaded with the chunk's X, so no global
 // read sits inside the softmax chain.
+//
+// Bias grads and loss, two forms:
+//   SINGLE = false (many chunks per step, mlp_train_steps_kernel): they are
+//     accumulated in L.db1 / L.db2 / L.loss, which the caller zeroes per
+//     step, and the function ends in a workgroup barrier after which the
+//     chunk arrays may be refilled.
+//   SINGLE = true (the step is this one chunk): the summing wave hands them
+//     back in a register instead. Thread t = BIAS_SUM_T0 + i, i < PART, gets
+//     in bias_sum entry i of db1 | db2 | loss (PART layout), every other
+//     thread 0. L.db1 / L.db2 / L.loss are not touched, and there is NO
+//     trailing barrier: each wave returns straight after its last MFMA, so
+//     the caller must put a workgroup barrier before it reuses any chunk
+//     array.
+constexpr int BIAS_SUM_T0 = (NWAVE - 1) * 64;
+
+template <bool SINGLE>
 __device__ __forceinline__ void chunk_fwd_bwd(
     const Lds& L, const float* b1, const float* b2,
-    const int label, const bool valid, float invBtot, ChunkAcc& acc_io) {
+    const int label, const bool valid, float invBtot, ChunkAcc& acc_io,
+    float& bias_sum) {
   const int tid = threadIdx.x;
   const int wave = tid >> 6;
   const int l = tid & 63;
   const int lg = l >> 4, lr = l & 15;
   const int wrow = wave * 16;                       // this wave's 16-row block
 
+  // this lane's bias values, ahead of everything that needs them: the eight
+  // b1[mt*16 + lg*4 + r] as two 16-byte reads and the four b2[lg*4 + r] as
+  // one (b2 holds CPAD floats, so the read is in range for every lg; the
+  // pad is masked in head_logits_padded). They are issued with fwd1's
+  // fragment reads and have long arrived where they are added; read where
+  // they are used, each cost an LDS round trip inside the dependent chain.
+  // The scheduling barriers keep the order bias reads, fragment reads,
+  // MFMAs: left to the scheduler the bias reads sink below the MFMAs, next
+  // to their adds.
+  bf16x8 w1f[HID / 16][IN / 32], xf[IN / 32];
+  f32x4 b1v[HID / 16];
+  #pragma unroll
+  for (int mt = 0; mt < HID / 16; ++mt) b1v[mt] = *(const f32x4*)&b1[mt * 16 + lg * 4];
+  const f32x4 b2v = *(const f32x4*)&b2[lg * 4];
+  __builtin_amdgcn_sched_barrier(0);
+  #pragma unroll
+  for (int ks = 0; ks < IN / 32; ++ks) {
+    xf[ks] = *(const bf16x8*)&L.Xs[wrow + lr][ks * 32 + lg * 8];
+    #pragma unroll
+    for (int mt = 0; mt < HID / 16; ++mt) {
+      w1f[mt][ks] = *(const bf16x8*)&L.W1T[mt * 16 + lr][ks * 32 + lg * 8];
+    }
+  }
+  __builtin_amdgcn_sched_barrier(0);
+
   // ---- fwd1: H^T = W1T @ B(Xs);  D: h = mt*16+lg*4+r, row = wrow+lr --------
+  // hbits keeps the lane's eight H values: dH below needs exactly these
+  // (same h, same row), so it does not read HT back
+  u16 hbits[HID / 16][4];
+  f32x4 hacc[HID / 16];
   #pragma unroll
   for (int mt = 0; mt < HID / 16; ++mt) {
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    hacc[mt] = (f32x4){0.f, 0.f, 0.f, 0.f};
     #pragma unroll
     for (int ks = 0; ks < IN / 32; ++ks) {
-      const bf16x8 a = *(const bf16x8*)&L.W1T[mt * 16 + lr][ks * 32 + lg * 8];
-      const bf16x8 b = *(const bf16x8*)&L.Xs[wrow + lr][ks * 32 + lg * 8];
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc, 0, 0, 0);
+      hacc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1f[mt][ks], xf[ks], hacc[mt], 0, 0, 0);
     }
+  }
+  #pragma unroll
+  for (int mt = 0; mt < HID / 16; ++mt) {
     #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int h = mt * 16 + lg * 4 + r;
       const int row = wrow + lr;
-      float hv = acc[r] + b1[h];
+      float hv = hacc[mt][r] + b1v[mt][r];
       hv = hv > 0.f ? hv : 0.f;
       const u16 hb = f2bf(hv);
-      L.Hs[row][h] = hb;
+      hbits[mt][r] = hb;
       L.HT[h][row] = hb;
     }
+    store_bf16x4(&L.Hs[wrow + lr][mt * 16 + lg * 4], hbits[mt]);
   }
   // NO __syncthreads here: fwd2 reads only THIS wave's rows of Hs
   // (row = wrow+lr), written by lanes of the same wave — a wave-level
@@ -450,23 +520,25 @@ __device__ __forceinline__ void chunk_fwd_bwd(
     const int row = wrow + lr;
 
     float logit[1][4], e[1][4];
-    head_logits<1>(logit, acc, b2, CLS, lg);
+    head_logits_padded(logit, acc, b2v, CLS, lg);
     const float m = head_row_max<1>(logit);
     const float s = head_exp_sum<1>(e, logit, m, CLS, lg);
     const float rs = fast_rcp(s);
     const float logs = __logf(s);
     float db2_acc[4];
     float loss_acc = 0.f;
+    u16 dlbits[4];
     #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int c = lg * 4 + r;
       const float dl = valid ? (e[0][r] * rs - (c == label ? 1.f : 0.f)) * invBtot : 0.f;
       const u16 dlb = f2bf(dl);
-      L.DLs[row][c] = dlb;
+      dlbits[r] = dlb;
       L.DLT[c][row] = dlb;
       db2_acc[r] = dl;
       if (valid && c == label) loss_acc = -(logit[0][r] - m - logs) * invBtot;
     }
+    store_bf16x4(&L.DLs[row][lg * 4], dlbits);
     // reduce db2/loss over the 16 row-lanes (lr bits) first, then ONE
     // plain store per (wave, class) into this wave's partial row: the
     // waves are summed in fixed order below, so the step is reproducible
@@ -504,7 +576,7 @@ __device__ __forceinline__ void chunk_fwd_bwd(
       for (int r = 0; r < 4; ++r) {
         const int h = mt * 16 + lg * 4 + r;
         const int row = wrow + lr;
-        const float hv = bf2f(L.HT[h][row]);
+        const float hv = bf2f(hbits[mt][r]);   // == L.HT[h][row], this lane's own store
         const float dh = hv > 0.f ? acc[r] : 0.f;
         L.DHT[h][row] = f2bf(dh);
         db1_acc[mt][r] = dh;
@@ -532,13 +604,20 @@ __device__ __forceinline__ void chunk_fwd_bwd(
 
   // ---- db1/db2/loss += partials, waves in fixed order. The last wave does
   // it: it has no dW2 tile, so this stays off the longest wave's path ----
+  bias_sum = 0.f;
   if (wave == NWAVE - 1 && l < PART) {
     float sum = 0.f;
     #pragma unroll
     for (int w = 0; w < NWAVE; ++w) sum += L.part[w * PART + l];
-    if (l < HID) L.db1[l] += sum;
-    else if (l < HID + CPAD) L.db2[l - HID] += sum;
-    else L.loss[0] += sum;
+    if constexpr (SINGLE) {
+      // what the accumulating form leaves in the zeroed LDS slot: 0 + sum
+      // (kept as written: 0 + (-0) is +0)
+      bias_sum = 0.f + sum;
+    } else {
+      if (l < HID) L.db1[l] += sum;
+      else if (l < HID + CPAD) L.db2[l - HID] += sum;
+      else L.loss[0] += sum;
+    }
   }
 
   // ---- dW1^T += DHT @ B(XT): wave tile (ht = w&1, it = w>>1) ---------------
@@ -564,7 +643,12 @@ __device__ __forceinline__ void chunk_fwd_bwd(
     }
     acc_io.dW2 = acc;
   }
-  __syncthreads();   // chunk arrays free for reuse
+  if constexpr (!SINGLE) __syncthreads();   // chunk arrays free for reuse
+}
+
+// flat grads/slab index of entry i of the PART layout (db1 | db2 | loss)
+__device__ __forceinline__ int bias_sum_index(int i) {
+  return i < HID ? OFF_B1 + i : i < HID + CPAD ? OFF_B2 + (i - HID) : OFF_LOSS;
 }
 
 // ---------------------------------------------------------------------------
@@ -587,9 +671,6 @@ mlp_step_kernel(const u16* __restrict__ Xbf, const int* __restrict__ y, int B,
   const int lg = l >> 4, lr = l & 15;
   const long long row0 = (long long)blockIdx.x * ROWS;
 
-  if (tid < HID) L.db1[tid] = 0.f;
-  if (tid < CPAD) L.db2[tid] = 0.f;
-  if (tid == 0) L.loss[0] = 0.f;
   XChunkRegs xr;
   issue_x_chunk(xr, Xbf, y, row0, B);
   const float bias = issue_biases(master + OFF_B1, master + OFF_B2);
@@ -602,7 +683,8 @@ mlp_step_kernel(const u16* __restrict__ Xbf, const int* __restrict__ y, int B,
   ChunkAcc acc;
   acc.dW1 = (f32x4){0.f, 0.f, 0.f, 0.f};
   acc.dW2 = (f32x4){0.f, 0.f, 0.f, 0.f};
-  chunk_fwd_bwd(L, L.b1s, L.b2s, chunk_label(xr), xr.valid, invBtot, acc);
+  float bias_sum;
+  chunk_fwd_bwd<true>(L, L.b1s, L.b2s, chunk_label(xr), xr.valid, invBtot, acc, bias_sum);
 
   {
     const int ht = wave & 1, it = wave >> 1;
@@ -620,9 +702,10 @@ mlp_step_kernel(const u16* __restrict__ Xbf, const int* __restrict__ y, int B,
       atomicAdd(&grads[OFF_W2 + h * CPAD + lr], acc.dW2[r]);
     }
   }
-  if (tid < HID) atomicAdd(&grads[OFF_B1 + tid], L.db1[tid]);
-  else if (tid < HID + CPAD) atomicAdd(&grads[OFF_B2 + tid - HID], L.db2[tid - HID]);
-  else if (tid == HID + CPAD) atomicAdd(&grads[OFF_LOSS], L.loss[0]);
+  // db1 / db2 / loss: the summing wave adds its register
+  if (tid >= BIAS_SUM_T0 && tid < BIAS_SUM_T0 + PART) {
+    atomicAdd(&grads[bias_sum_index(tid - BIAS_SUM_T0)], bias_sum);
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -654,31 +737,59 @@ mlp_step_kernel(const u16* __restrict__ Xbf, const int* __restrict__ y, int B,
 //       master are written only in the Adam phase, which no workgroup enters
 //       before ALL have published, i.e. after all have finished their
 //       prologue loads; the prefetched master/m/v stripe is written only by
-//       the workgroup that reads it; counter and t_dev are written by
-//       workgroup 0 as its last act, after every workgroup has published and
-//       so has read them.
+//       the workgroup that reads it; counter and t_dev are loaded by EVERY
+//       thread (one plain vector load each, issued with the prologue loads)
+//       and every wave has consumed its two words before it reaches the
+//       FIRST barrier of its workgroup, hence before that workgroup
+//       publishes; they are written by workgroup 0 as its last act, after
+//       every workgroup has published and so has read them.
+// Barriers, four per launch: after the prologue's LDS fills; after dH (DHT
+// and the per-wave partials complete); the publish barrier of (2); and the
+// one the polling wave joins once its poll has matched. Between the second
+// and the third each wave goes from its last MFMA straight to its slab
+// stores (chunk_fwd_bwd<true> ends in no barrier; the summing wave stores
+// db1 / db2 / loss from a register).
 // ---------------------------------------------------------------------------
 
 extern "C" __global__ void __launch_bounds__(BLOCK)
-mlp_step_fused_kernel(const u16* __restrict__ Xbf, const int* __restrict__ y,
+mlp_step_fused_kernel(// the seven arguments the prologue's vector loads need
+                      // come first: 14 dwords, inside the 16 that the build's
+                      // kernel-argument preload delivers in registers at
+                      // wave start (setup.py)
+                      const u16* __restrict__ Xbf, const int* __restrict__ y,
                       int B,
-                      const u16* __restrict__ W1bf, const u16* __restrict__ W2bf,
-                      float* __restrict__ master, u16* __restrict__ bfmirror,
-                      float* __restrict__ m, float* __restrict__ v,
+                      u16* __restrict__ wimg,          // optional packed images
+                      float* __restrict__ master,
+                      unsigned* __restrict__ counter,  // launch-epoch counter (both modes)
                       int* __restrict__ t_dev,
+                      const u16* __restrict__ W1bf, const u16* __restrict__ W2bf,
+                      u16* __restrict__ bfmirror,
+                      float* __restrict__ m, float* __restrict__ v,
                       float* __restrict__ slabs,    // [n_wg][SLAB]
-                      unsigned* __restrict__ counter,  // launch-epoch counter (reduce-only mode)
                       float* __restrict__ loss_out,
                       float invBtot, float lr, float beta1, float beta2,
                       float eps,
-                      float* __restrict__ grads_out, // non-null: write summed
-                                                       // grads (+loss) and skip
-                                                       // Adam — the DP path's
-                                                       // pre-collective kernel
-                      u16* __restrict__ wimg) {        // optional packed images
+                      // non-null: write summed grads (+loss) and skip
+                      // Adam — the DP path's pre-collective kernel
+                      float* __restrict__ grads_out) {
+  // ---- prologue, phase 0: the kernel arguments. Left alone the compiler
+  // fetches an argument just before its first use: a second batch (wimg,
+  // master, counter, t_dev) stood between the X loads and the image loads,
+  // and stragglers (invBtot, the Adam scalars) waited in the middle of the
+  // softmax. An empty asm statement uses its operands, so their scalar
+  // loads and ONE wait for them sit above it. The seven arguments of the
+  // vector loads below are pinned here: preloaded (setup.py) they are in
+  // registers already and nothing waits; in a build without the preload, or
+  // on firmware without it (the kernel's compatibility entry), they arrive
+  // in one scalar round trip. The other arguments are pinned behind the
+  // vector loads, so that their round trip runs beside those. ---------------
+  asm volatile("" :: "s"(Xbf), "s"(y), "s"(B), "s"(wimg), "s"(master), "s"(counter),
+               "s"(t_dev));
+
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const Lds L = carve(smem);
-  // L.loss slots: [0] loss accum, [1] (bits) poll base, [2] t_pre, [3] unused
+  // L.loss slots: [0] unused here (the loss travels in a register),
+  // [1] poll verdict (0 ok, 1 timed out)
   unsigned* lossu = (unsigned*)L.loss;
 
   const int tid = threadIdx.x;
@@ -686,12 +797,11 @@ mlp_step_fused_kernel(const u16* __restrict__ Xbf, const int* __restrict__ y,
   const int l = tid & 63;
   const int lg = l >> 4, lr_ = l & 15;
   const long long row0 = (long long)blockIdx.x * ROWS;
-  const int n_wg = gridDim.x;
 
   // ---- prologue, phase 1: EVERY global load goes out before the first
   // wait (after the launch-boundary invalidate each one is a cold round
   // trip, so they must overlap): X vectors + label, packed images, bias
-  // element, and thread 0's epoch / step counters ----------------------------
+  // element, and the epoch / step counters -----------------------------------
   XChunkRegs xr;
   WimgRegs wr;
 #ifndef PROBE_SKIP_LOADS
@@ -701,21 +811,27 @@ mlp_step_fused_kernel(const u16* __restrict__ Xbf, const int* __restrict__ y,
   issue_label(xr, y, row0, B);   // timing probe: X and the images stay out
 #endif
   const float bias = issue_biases(master + OFF_B1, master + OFF_B2);
-  unsigned counter_pre = 0u, t_pre = 0u;
-  if (tid == 0) {
-    // read the epoch source BEFORE any workgroup of this launch can have
-    // advanced it (the writer only writes after every WG has published,
-    // i.e. after every WG has passed this point). BOTH modes use the
-    // dedicated launch counter, so mixing fused-Adam and reduce-only
-    // launches on one model keeps epochs unique and monotonic; t_dev is
-    // read separately for Adam bias correction only.
-    counter_pre = *counter;
-    t_pre = (unsigned)(*t_dev);
-  }
+  // Read the epoch source BEFORE any workgroup of this launch can have
+  // advanced it (the writer only writes after every WG has published, i.e.
+  // after every wave of every WG has consumed this load: it is waited for
+  // below, ahead of the first barrier). BOTH modes use the dedicated launch
+  // counter, so mixing fused-Adam and reduce-only launches on one model
+  // keeps epochs unique and monotonic; t_dev is read separately for Adam
+  // bias correction only. EVERY thread loads both words (one uniform
+  // address, one vector load in flight with the others): the values live in
+  // a register of every thread, nothing waits on a scalar load of its own
+  // and nothing travels through LDS.
+  const unsigned counter_pre = uniform_load(counter);
+  const unsigned t_pre = (unsigned)uniform_load(t_dev);
+  // every other argument, the implicit grid size included: one scalar round
+  // trip in the shadow of the vector loads above; no fetch of an argument
+  // is left behind the first barrier
+  const int n_wg = gridDim.x;
+  asm volatile("" :: "s"(W1bf), "s"(W2bf), "s"(bfmirror), "s"(m), "s"(v), "s"(slabs),
+               "s"(loss_out), "s"(invBtot), "s"(lr), "s"(beta1), "s"(beta2), "s"(eps),
+               "s"(grads_out), "s"(n_wg));
 
   // ---- phase 2: LDS fills that need no load, then the loaded registers ----
-  if (tid < HID) L.db1[tid] = 0.f;
-  if (tid < CPAD) L.db2[tid] = 0.f;
   zero_dl_pad(L);
 #ifndef PROBE_SKIP_LOADS
   if (wimg) store_weight_images_packed(wr, L);
@@ -723,18 +839,23 @@ mlp_step_fused_kernel(const u16* __restrict__ Xbf, const int* __restrict__ y,
   store_x_chunk(xr, L);
 #endif
   store_biases(bias, L);
-  if (tid == 0) {
-    L.loss[0] = 0.f;
-    lossu[2] = counter_pre;
-    lossu[3] = t_pre;
-  }
+  // This launch's epoch, unique per launch (exactly one WG advances the
+  // counter per launch). The asm uses it, so every wave has its counter
+  // word before it can reach the barrier.
+  const unsigned epoch = counter_pre + 1u;
+  asm volatile("" :: "v"(epoch), "v"(t_pre));
   __syncthreads();
 
   ChunkAcc acc;
   acc.dW1 = (f32x4){0.f, 0.f, 0.f, 0.f};
   acc.dW2 = (f32x4){0.f, 0.f, 0.f, 0.f};
+  float bias_sum = 0.f;
 #ifndef PROBE_SKIP_FWDBWD
-  chunk_fwd_bwd(L, L.b1s, L.b2s, chunk_label(xr), xr.valid, invBtot, acc);
+  // single-chunk form: no barrier at its end. Each wave goes from its last
+  // MFMA straight to its slab stores below; the next workgroup barrier is
+  // the publish barrier, and the chunk arrays are reused only behind it
+  // (the Adam-state prefetch into Xs).
+  chunk_fwd_bwd<true>(L, L.b1s, L.b2s, chunk_label(xr), xr.valid, invBtot, acc, bias_sum);
 #endif
 
   // ---- write this WG's complete partial slab: write-through (sc1) stores,
@@ -761,17 +882,16 @@ mlp_step_fused_kernel(const u16* __restrict__ Xbf, const int* __restrict__ y,
       xwg_store(&slab[OFF_W2 + h * CPAD + lr_], acc.dW2[r]);
     }
   }
-  if (tid < HID) xwg_store(&slab[OFF_B1 + tid], L.db1[tid]);
-  else if (tid < HID + CPAD) xwg_store(&slab[OFF_B2 + tid - HID], L.db2[tid - HID]);
-  else if (tid == HID + CPAD) xwg_store(&slab[OFF_LOSS], L.loss[0]);
+  // db1 / db2 / loss: the summing wave stores its register
+  if (tid >= BIAS_SUM_T0 && tid < BIAS_SUM_T0 + PART) {
+    xwg_store(&slab[bias_sum_index(tid - BIAS_SUM_T0)], bias_sum);
+  }
 
   // ---- signal + all-WG barrier (guide §6 G16, write-through form: sc1
   // payload, every storing wave drains, ONE lane stores the per-slab epoch
   // tag sc1). The tag is this launch's epoch counter_pre+1 — unique per
-  // launch (exactly one WG advances the counter per launch), so the scheme
-  // is robust to any grid size, graph replay, and engine mixing; no
-  // reset. --------------------------------------------------------------------
-  const unsigned epoch = lossu[2] + 1u;
+  // launch, so the scheme is robust to any grid size, graph replay, and
+  // engine mixing; no reset. ---------------------------------------------------
   // Adam-state prefetch scratch (loads issued during the sweep below);
   // the chunk arrays are dead from here on — reuse Xs
   float* pre = (float*)L.Xs;
@@ -846,12 +966,12 @@ mlp_step_fused_kernel(const u16* __restrict__ Xbf, const int* __restrict__ y,
 #ifdef PROBE_SKIP_REDUCE
   if (tid == 0 && blockIdx.x == 0) {
     *counter = epoch;
-    if (!grads_out) *t_dev = (int)(lossu[3] + 1u);
+    if (!grads_out) *t_dev = (int)(t_pre + 1u);
   }
   return;
 #endif
   // ---- every WG reduces its own param stripe + applies Adam ----------------
-  const float t_new = (float)(lossu[3] + 1u);
+  const float t_new = (float)(t_pre + 1u);
   float corr1, corr2;
   adam_bias_corr(beta1, beta2, t_new, corr1, corr2);
   const int span = (NPARAM + 1 + n_wg - 1) / n_wg;
@@ -1048,8 +1168,9 @@ mlp_train_steps_kernel(const u16* __restrict__ Xbf,  // [N][IN] staged bf16
       issue_x_chunk(xr, Xbf, y, row0, N);
       store_x_chunk(xr, L);
       __syncthreads();
-      chunk_fwd_bwd(L, master_s + OFF_B1, master_s + OFF_B2, chunk_label(xr), xr.valid,
-                    invB, acc);
+      float unused;
+      chunk_fwd_bwd<false>(L, master_s + OFF_B1, master_s + OFF_B2, chunk_label(xr),
+                           xr.valid, invB, acc, unused);
     }
 
     // ---- fused in-LDS Adam --------------------------------------------------
@@ -1289,9 +1410,9 @@ int launch_mlp_step_fused(const unsigned short* Xbf, const int* y, int B,
     done = 1;
   }
   hipLaunchKernelGGL(mlp_step_fused_kernel, dim3(blocks), dim3(BLOCK), C_IMG_TOTAL,
-                     stream, Xbf, y, B, W1bf, W2bf, master, bfmirror, m, v, t_dev,
-                     slabs, counter, loss_out, invBtot, lr, beta1, beta2, eps,
-                     grads_out, wimg);
+                     stream, Xbf, y, B, wimg, master, counter, t_dev, W1bf, W2bf,
+                     bfmirror, m, v, slabs, loss_out, invBtot, lr, beta1, beta2, eps,
+                     grads_out);
   return 0;
 }
 
