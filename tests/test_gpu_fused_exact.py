@@ -332,10 +332,10 @@ def test_reallocating_slabs_drops_the_captured_graph(ext, dev):
 @pytest.mark.parametrize("n_wg", [1, 5, 9])
 @pytest.mark.parametrize("shape", [(1, 1, 2), (100, 50, 7)], ids=["1x1x2", "100x50x7"])
 def test_gen_full_mode_equals_reduce_only_plus_adam_step_gen(ext, dev, shape, n_wg):
-    """The gen step kernel still sums db1, db2 and the loss with LDS atomics,
-    so two launches of it are not comparable bit for bit; the slabs are
-    written by hand instead (as test_gpu_oracle.py::test_reduce_gen_sum_vs_fp64
-    does): values over 6 decades, mixed signs, a fresh set per step.
+    """The slabs are written by hand (as
+    test_gpu_oracle.py::test_reduce_gen_sum_vs_fp64 does), so that the two
+    paths are compared on sums harder than a step kernel produces: values
+    over 6 decades, mixed signs, a fresh set per step.
     reduce_adam_gen in full mode against reduce_adam_gen(grads_out=) +
     adam_step_gen, three steps."""
     from unionml_amd.ops.tabular import TabularMLP

@@ -117,9 +117,9 @@ def test_gen_reduce_mode_matches_fused(ext, dev, shape):
         b._adam(1e-3)
     torch.cuda.synchronize()
     assert int(a.t_dev.item()) == 3 and int(b.t_dev.item()) == 3
-    assert torch.allclose(a.master, b.master, rtol=0, atol=1e-7), (
-        (a.master - b.master).abs().max().item()
-    )
+    # the step's sums are order-fixed and both paths share adam_update: same bits
+    assert torch.equal(a.master, b.master), (a.master - b.master).abs().max().item()
+    assert torch.equal(a.m, b.m) and torch.equal(a.v, b.v)
     # packed weight images must agree too (maintained by different kernels)
     assert torch.equal(a.wimg, b.wimg)
 
@@ -179,8 +179,9 @@ def test_gen_graph_vs_eager(ext, dev):
             Xbf, y.to(dev), epochs=8, batch_size=512, lr=2e-3, use_graph=use_graph
         )
         results[use_graph] = (loss, clf.master.cpu())
-    assert abs(results[True][0] - results[False][0]) < 5e-2
-    assert torch.allclose(results[True][1], results[False][1], atol=1e-5)
+    # a replayed graph runs the launches the eager epochs run: same bits
+    assert results[True][0] == results[False][0]
+    assert torch.equal(results[True][1], results[False][1])
 
 
 def test_gen_wimg_stays_consistent(ext, dev):

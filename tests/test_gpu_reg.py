@@ -66,9 +66,9 @@ def test_reduce_mode_matches_fused(ext, dev, shape):
         b._adam(1e-3)
     torch.cuda.synchronize()
     assert int(a.t_dev.item()) == STEPS and int(b.t_dev.item()) == STEPS
-    assert torch.allclose(a.master, b.master, rtol=0, atol=1e-7), (
-        (a.master - b.master).abs().max().item()
-    )
+    # the step's sums are order-fixed and both paths share adam_update: same bits
+    assert torch.equal(a.master, b.master), (a.master - b.master).abs().max().item()
+    assert torch.equal(a.m, b.m) and torch.equal(a.v, b.v)
     for reg in (a, b):
         incremental = reg.wimg.clone()
         reg._build_wimg()
@@ -89,8 +89,9 @@ def test_graph_vs_eager_and_state_roundtrip(ext, dev, shape):
                                 use_graph=use_graph)
         assert int(reg.t_dev.item()) == STEPS and loss == loss
         results[use_graph] = (loss, reg.master.cpu(), reg)
-    assert abs(results[True][0] - results[False][0]) < 5e-2
-    assert torch.allclose(results[True][1], results[False][1], atol=1e-5)
+    # a replayed graph runs the launches the eager epochs run: same bits
+    assert results[True][0] == results[False][0]
+    assert torch.equal(results[True][1], results[False][1])
 
     reg = results[True][2]
     rebuilt = make_reg(shape, dev, seed=99)

@@ -79,6 +79,9 @@ struct GG {
   static constexpr int DHS = RT + 8;    // DHT       [HID][DHS]
   static constexpr int W2S = 40;        // W2s       [HID][40]  (K-pad to 32)
   static constexpr int W2T = HID + 8;   // W2T       [CPAD][W2T]
+  // per-row-tile partial sums (f32 elems): part [RT/16][PS], one row per
+  // 16-row tile holding its db1 [HID], db2 [CPAD] and loss [1]
+  static constexpr int PS = HID + CPAD + 1;
 
   // streamed-tile buffer sizes (u16 elems, ONE buffer each)
   static constexpr int XBUF1 = IMAX(RT * XSS, TK * XTS);
@@ -94,9 +97,7 @@ struct GG {
     o = A16(o + HID * DHS * 2);
     o = A16(o + HID * W2S * 2);
     o = A16(o + CPAD * W2T * 2);
-    o = A16(o + HID * 4);
-    o = A16(o + CPAD * 4);
-    o = A16(o + 16);
+    o = A16(o + (RT / 16) * PS * 4);
     o = A16(o + HID * 4);
     return A16(o + CPAD * 4);
   }
@@ -117,10 +118,8 @@ struct GG {
   static constexpr int O_DH = A16(O_DT + CPAD * DTS * 2);
   static constexpr int O_2S = A16(O_DH + HID * DHS * 2);
   static constexpr int O_2T = A16(O_2S + HID * W2S * 2);
-  static constexpr int O_B1G = A16(O_2T + CPAD * W2T * 2);   // db1 [HID] f32
-  static constexpr int O_B2G = A16(O_B1G + HID * 4);         // db2 [CPAD] f32
-  static constexpr int O_LS = A16(O_B2G + CPAD * 4);         // loss slots (4 f32)
-  static constexpr int O_B1 = A16(O_LS + 16);                // b1 stage [HID]
+  static constexpr int O_PT = A16(O_2T + CPAD * W2T * 2);    // part [RT/16][PS] f32
+  static constexpr int O_B1 = A16(O_PT + (RT / 16) * PS * 4);  // b1 stage [HID]
   static constexpr int O_B2 = A16(O_B1 + HID * 4);           // b2 stage [CPAD]
   static constexpr int TOTAL = A16(O_B2 + CPAD * 4);
   static_assert(TOTAL == layout_total(NXB), "layout helper out of sync");
@@ -132,6 +131,21 @@ struct GG {
   static_assert(RT % 32 == 0, "RT must be a multiple of 32");
   static_assert(TOTAL <= 160 * 1024, "LDS carve exceeds 160 KB");
 
+  // What the per-tile partial rows cost over the three accumulators they
+  // replaced (db1 [HID], db2 [CPAD] and four loss slots, each 16-aligned):
+  // under 3,104 bytes everywhere (the whole of part at <64,128,32>), the
+  // largest carve (<256,32,32>) stays under 151,064 bytes, every geometry
+  // that double-buffered still does, and as many workgroups fit a CU's
+  // 160 KB as before.
+  static constexpr int PART_BYTES = (RT / 16) * PS * 4;
+  static constexpr int PART_EXTRA = A16(PART_BYTES) - (HID * 4 + CPAD * 4 + 16);
+  static_assert(PART_BYTES <= 3104 && PART_EXTRA <= 3104, "partial rows grew");
+  static_assert(TOTAL <= 151064, "largest carve grew");
+  static_assert(DB || layout_total(2) - PART_EXTRA > 160 * 1024,
+                "partial rows cost a geometry its double buffer");
+  static_assert((160 * 1024) / TOTAL == (160 * 1024) / (TOTAL - PART_EXTRA),
+                "partial rows cost a workgroup per CU");
+
   char* smem_;
   u16 (*Hs)[HSS];
   u16 (*HT)[HTS];
@@ -140,9 +154,7 @@ struct GG {
   u16 (*DHT)[DHS];
   u16 (*W2s)[W2S];
   u16 (*W2Tt)[W2T];
-  float* db1;
-  float* db2;
-  float* loss;
+  float (*part)[PS];
   float* b1s;
   float* b2s;
 
@@ -165,9 +177,7 @@ struct GG {
     DHT = (u16(*)[DHS])(smem + O_DH);
     W2s = (u16(*)[W2S])(smem + O_2S);
     W2Tt = (u16(*)[W2T])(smem + O_2T);
-    db1 = (float*)(smem + O_B1G);
-    db2 = (float*)(smem + O_B2G);
-    loss = (float*)(smem + O_LS);
+    part = (float(*)[PS])(smem + O_PT);
     b1s = (float*)(smem + O_B1);
     b2s = (float*)(smem + O_B2);
   }
@@ -268,6 +278,20 @@ __device__ __forceinline__ void zero_dl_pad(const G& L) {
 // targets. What a row's target is differs with it: an int label y[N], or
 // fp32 standardized targets Yt[N][CPAD], pad columns zero. Everything
 // outside the fwd2 epilogue is shared.
+//
+// Summation order (both heads, every instantiation). A workgroup's db1,
+// db2 and loss are sums over its RT/16 row tiles of 16 rows. Each tile's
+// partial (its 16 rows summed by row_sum16's fixed butterfly, the loss also
+// over the lane groups) is STORED to the tile's own row of L.part by one
+// lane; nothing is accumulated in arrival order. The last block of the
+// kernel adds the rows tile 0 first, left to right,
+//   ((part[0] + part[1]) + part[2]) + ... + part[RT/16 - 1],
+// one fp32 rounding per addition, and writes the slab entry. A tile of tail
+// rows only contributes an exact zero. With reduce_adam_gen's fixed slab
+// order this makes the step bit-reproducible by construction
+// (tests/test_gpu_gen_order.py holds the kernel to this order bit for bit).
+// The stores and the final sum lie outside the head's if constexpr: keep
+// them shared, the classifier head has no exact probe of its own.
 template <int HID, int RT, int CP, int HEAD = HEAD_XENT>
 __global__ void __launch_bounds__(512)
 mlp_step_gen_kernel(const u16* __restrict__ Xbf,   // [N][inp] staged bf16 (zero-padded)
@@ -293,9 +317,6 @@ mlp_step_gen_kernel(const u16* __restrict__ Xbf,   // [N][inp] staged bf16 (zero
   const int off_b2 = off_w2 + HID * G::CPAD;
   const int nparam = off_b2 + G::CPAD;
 
-  for (int i = tid; i < HID; i += G::BLOCK) L.db1[i] = 0.f;
-  if (tid < G::CPAD) L.db2[tid] = 0.f;
-  if (tid == 0) L.loss[0] = 0.f;
   zero_dl_pad(L);
   load_w2_images(L, wimg, inp);
   for (int i = tid; i < HID; i += G::BLOCK) L.b1s[i] = master[off_b1 + i];
@@ -454,7 +475,10 @@ mlp_step_gen_kernel(const u16* __restrict__ Xbf,   // [N][inp] staged bf16 (zero
         }
       }
     }
-    // in-row sums first (DPP, every lane active), predicated atomics after
+    // in-row sums first (DPP, every lane active), predicated stores after:
+    // this tile's db2 and loss partials go to its own row of L.part, one
+    // writing lane per entry (shared by both heads: the if constexpr above
+    // has ended)
     #pragma unroll
     for (int ct = 0; ct < G::NCT; ++ct) {
       #pragma unroll
@@ -466,13 +490,13 @@ mlp_step_gen_kernel(const u16* __restrict__ Xbf,   // [N][inp] staged bf16 (zero
       for (int ct = 0; ct < G::NCT; ++ct) {
         #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          atomicAdd(&L.db2[ct * 16 + lg * 4 + r], db2_acc[ct][r]);
+          L.part[t2][HID + ct * 16 + lg * 4 + r] = db2_acc[ct][r];
         }
       }
     }
     loss_acc = group_sum<16>(loss_acc);
     loss_acc = group_sum<32>(loss_acc);
-    if (l == 0) atomicAdd(L.loss, loss_acc);
+    if (l == 0) L.part[t2][HID + G::CPAD] = loss_acc;
   }
   __syncthreads();
 
@@ -499,7 +523,7 @@ mlp_step_gen_kernel(const u16* __restrict__ Xbf,   // [N][inp] staged bf16 (zero
       }
       if (lr_ == 0) {
         #pragma unroll
-        for (int r = 0; r < 4; ++r) atomicAdd(&L.db1[mt * 16 + lg * 4 + r], db1_acc[r]);
+        for (int r = 0; r < 4; ++r) L.part[rt][mt * 16 + lg * 4 + r] = db1_acc[r];
       }
     }
   }
@@ -527,7 +551,7 @@ mlp_step_gen_kernel(const u16* __restrict__ Xbf,   // [N][inp] staged bf16 (zero
 
   // ---- dW1^T = DHT @ B(XT), K'-streamed over inp -> slab -------------------
   // (tile 0 was prefetched before fwd2; the barrier below also covers
-  // the dH-phase atomics)
+  // the dH phase's db1 partials)
   __syncthreads();
   for (int kt = 0; kt < nkt; ++kt) {
     const int cur = G::DB ? (kt & 1) : 0;
@@ -566,11 +590,17 @@ mlp_step_gen_kernel(const u16* __restrict__ Xbf,   // [N][inp] staged bf16 (zero
     }
   }
 
-  // ---- bias grads + loss into the slab -------------------------------------
-  for (int i = tid; i < HID; i += G::BLOCK) slab[off_b1 + i] = L.db1[i];
-  if (tid < G::CPAD) slab[off_b2 + tid] = L.db2[tid];
-  if (tid == G::CPAD) slab[nparam] = L.loss[0];
-
+  // ---- bias grads + loss into the slab: the row tiles' partials summed in
+  // tile order, ((p0 + p1) + p2) + ..., by one thread per entry (part is
+  // complete: every tile, an all-tail one included, stored its row, and the
+  // barriers of the dW1 loop lie between those stores and here) -------------
+  for (int i = tid; i < HID + G::CPAD + 1; i += G::BLOCK) {
+    float s = L.part[0][i];
+    #pragma unroll
+    for (int j = 1; j < RT / 16; ++j) s += L.part[j][i];
+    const int at = i < HID ? off_b1 + i : i < HID + G::CPAD ? off_b2 + (i - HID) : nparam;
+    slab[at] = s;
+  }
 }
 
 // ---------------------------------------------------------------------------
