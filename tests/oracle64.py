@@ -294,7 +294,7 @@ def reference_step(case) -> torch.Tensor:
 
 SPEC_SHAPE = (64, 32, 10)
 
-# every STEP_CASE of tabular_gen.hip, <HID, RT, CPAD> -> one geometry. The
+# every step row of TABULAR_GEN_INSTANTIATIONS, <HID, RT, CPAD> -> one geometry. The
 # instantiations TabularMLP already reaches at test batch sizes come first,
 # the five only a direct rt= call reaches last. Together the geometries
 # cover: inp = 32 (half a TK=64 tile / one TK=32 tile), one full tile, two
@@ -316,7 +316,7 @@ STEP_INSTANTIATIONS = [
     ((256, 32, 32), (30, 256, 20)),
 ]
 
-# every PRED_CASE, <HID, RT, CPAD> -> geometry (the two never launched
+# every predict row, <HID, RT, CPAD> -> geometry (the two never launched
 # before come last)
 PRED_INSTANTIATIONS = [
     ((32, 128, 16), (64, 17, 16)),
@@ -400,6 +400,31 @@ def check_instantiation(inst, shape):
     """The geometry really selects the instantiation it is listed under."""
     g = Geometry(*shape)
     assert (g.hid, g.cpad) == (inst[0], inst[2]), (inst, shape)
+
+
+def header_instantiations():
+    """([step <HID, RT, CPAD>], [predict <HID, RT, CPAD>]) as the one table
+    macro of hip/tabular_launch.h lists them, and, checked on the way, that
+    tabular_gen.hip holds no list of its own: its dispatch helpers are
+    instantiated through the macro's parameters only, once per dispatcher."""
+    import re
+    from pathlib import Path
+
+    hip = Path(ref.__file__).parent / "hip"
+    header = (hip / "tabular_launch.h").read_text()
+    macro = re.search(r"#define TABULAR_GEN_INSTANTIATIONS\(X\)((?:.*\\\n)+.*\n)", header)
+    rows = [tuple(map(int, m)) for m in
+            re.findall(r"X\((\d+), (\d+), (\d+), ([01])\)", macro.group(1))]
+    assert len(re.findall(r"\bX\(", macro.group(1))) == len(rows)
+
+    src = (hip / "tabular_gen.hip").read_text()
+    assert len(re.findall(r"TABULAR_GEN_INSTANTIATIONS\(", src)) == 2
+    assert re.findall(r"launch_step_gen_t<([^>]*)>", src) == ["H, R, C, HEAD"]
+    assert re.findall(r"launch_predict_gen_t<([^>]*)>", src) == ["H, R, C, HEAD"]
+    uses = re.findall(r"mlp_(?:step|predict)_gen_kernel<([^>]*)>", src)
+    assert uses and set(uses) == {"HID, RT, CP, HEAD"}
+    assert not re.search(r"_CASE\(", src)
+    return [r[:3] for r in rows], [r[:3] for r in rows if r[3]]
 
 
 # Adam bound pieces ----------------------------------------------------------

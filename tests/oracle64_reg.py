@@ -142,8 +142,9 @@ def _as_targets(shape):
     return (20, 32, 1) if tuple(shape) == (20, 32, 2) else tuple(shape)
 
 
-# oracle64's geometries with the class count read as T: every STEP_REG_CASE /
-# PRED_REG_CASE of tabular_gen.hip once; T covers 1, 16, 17 and 32
+# oracle64's geometries with the class count read as T: every row of the
+# instantiation table (tabular_launch.h) once, for the regression head; T
+# covers 1, 16, 17 and 32
 STEP_INSTANTIATIONS = [(inst, _as_targets(s)) for inst, s in o64.STEP_INSTANTIATIONS]
 PRED_INSTANTIATIONS = [(inst, _as_targets(s)) for inst, s in o64.PRED_INSTANTIATIONS]
 

@@ -122,7 +122,7 @@ GEN_STEP = o64.gen_step_cases()
 
 @pytest.mark.parametrize("cid,inst,shape,B,seed", GEN_STEP, ids=[c[0] for c in GEN_STEP])
 def test_gen_step_vs_oracle(ext, dev, cid, inst, shape, B, seed):
-    """Every STEP_CASE instantiation <HID,RT,CPAD>, launched directly."""
+    """Every step instantiation <HID,RT,CPAD>, launched directly."""
     case = o64.make_case(shape, B, seed)
     o64.check_instantiation(inst, shape)
     check_step(cid, case, run_gen_step(ext, dev, case, inst[1]))
@@ -189,7 +189,7 @@ PREDICT = o64.predict_cases()
 
 @pytest.mark.parametrize("cid,inst,shape,B,seed", PREDICT, ids=[c[0] for c in PREDICT])
 def test_predict_vs_oracle(ext, dev, cid, inst, shape, B, seed):
-    """Every PRED_CASE instantiation and the specialized predict kernel."""
+    """Every predict instantiation and the specialized predict kernel."""
     case = o64.make_case(shape, B, seed)
     if inst is not None:
         o64.check_instantiation(inst, shape)

@@ -122,7 +122,7 @@ STEP = o64r.step_cases()
 
 @pytest.mark.parametrize("cid,inst,shape,B,seed", STEP, ids=[c[0] for c in STEP])
 def test_reg_step_vs_oracle(ext, dev, cid, inst, shape, B, seed):
-    """Every STEP_REG_CASE instantiation <HID,RT,CPAD>, launched directly."""
+    """Every regression step instantiation <HID,RT,CPAD>, launched directly."""
     case = o64r.make_case_reg(shape, B, seed)
     o64r.check_instantiation(inst, shape)
     check_step_reg(cid, case, run_reg_step(ext, dev, case, inst[1]))
@@ -157,7 +157,7 @@ PREDICT = o64r.predict_cases()
 
 @pytest.mark.parametrize("cid,inst,shape,B,seed", PREDICT, ids=[c[0] for c in PREDICT])
 def test_reg_predict_vs_oracle(ext, dev, cid, inst, shape, B, seed):
-    """Every PRED_REG_CASE instantiation with a fitted, far-from-identity
+    """Every regression predict instantiation with a fitted, far-from-identity
     target scaler, into an oversized pre-poisoned output: rows >= B and
     columns >= T stay untouched."""
     case = o64r.make_case_reg(shape, B, seed)

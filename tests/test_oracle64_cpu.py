@@ -72,14 +72,10 @@ def test_case_inputs():
 
 
 def test_case_matrix_covers_every_instantiation():
-    """The lists name every STEP_CASE / PRED_CASE of tabular_gen.hip once,
-    and each geometry selects the instantiation it is listed under."""
-    from pathlib import Path
-    import re
-
-    src = (Path(ref.__file__).parent / "hip" / "tabular_gen.hip").read_text()
-    step = [tuple(map(int, m)) for m in re.findall(r"^\s*STEP_CASE\((\d+), (\d+), (\d+)\)", src, re.M)]
-    pred = [tuple(map(int, m)) for m in re.findall(r"^\s*PRED_CASE\((\d+), (\d+), (\d+)\)", src, re.M)]
+    """The lists name every step / predict row of the instantiation table
+    (tabular_launch.h TABULAR_GEN_INSTANTIATIONS) once, and each geometry
+    selects the instantiation it is listed under."""
+    step, pred = o64.header_instantiations()
     assert len(step) == 11 and len(pred) == 8
     assert sorted(i for i, _ in o64.STEP_INSTANTIATIONS) == sorted(step)
     assert sorted(i for i, _ in o64.PRED_INSTANTIATIONS) == sorted(pred)

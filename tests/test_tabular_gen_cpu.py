@@ -205,3 +205,96 @@ def test_weights_only_checkpoint_resets_optimizer():
     assert int(fresh.t_dev.item()) == 0
     assert fresh.m.abs().max() == 0 and fresh.v.abs().max() == 0
     assert torch.equal(fresh.predict(X), clf.predict(X))
+
+
+# ---------------------------------------------------------------------------
+# the host layer's single sources: the instantiation table and the geometry
+# ---------------------------------------------------------------------------
+
+
+def test_python_table_equals_header():
+    """reference.GEN_INSTANTIATIONS is the table macro of tabular_launch.h,
+    row for row, and what is derived from it is what was written out before."""
+    import re
+    from pathlib import Path
+
+    header = (Path(ref.__file__).parent / "hip" / "tabular_launch.h").read_text()
+    macro = re.search(r"#define TABULAR_GEN_INSTANTIATIONS\(X\)((?:.*\\\n)+.*\n)", header)
+    rows = [(int(h), int(r), int(c), p == "1") for h, r, c, p in
+            re.findall(r"X\((\d+), (\d+), (\d+), ([01])\)", macro.group(1))]
+    assert len(rows) == 11 and sum(p for _, _, _, p in rows) == 8
+    assert list(ref.GEN_INSTANTIATIONS) == rows
+    assert len(set(r[:3] for r in rows)) == 11
+    assert ref.SUPPORTED_HID == (32, 64, 128, 256)
+    # PREDICT marks exactly the largest RT of each (HID, CPAD)
+    for h, r, c, p in rows:
+        assert p == (r == ref.compiled_rts(h, c)[-1]), (h, r, c)
+
+
+# {(inp, hid, cpad): (off_b1, off_w2, off_b2, nparam, image W2T offset, image
+# size)} for every padded geometry tests/oracle64.py runs. tabular_launch.h
+# holds its GenGeometry to the lines marked "header" in a static_assert, so
+# the C++ and the Python formulas meet in those numbers.
+HOST_GEOMETRY_LITERALS = {
+    (32, 32, 16): (1024, 1056, 1568, 1584, 2048, 2560),   # header
+    (32, 32, 32): (1024, 1056, 2080, 2112, 2048, 3072),   # header
+    (64, 32, 16): (2048, 2080, 2592, 2608, 3072, 3584),
+    (96, 64, 16): (6144, 6208, 7232, 7248, 8192, 9216),
+    (128, 64, 16): (8192, 8256, 9280, 9296, 10240, 11264),
+    (128, 64, 32): (8192, 8256, 10304, 10336, 10240, 12288),
+    (160, 64, 16): (10240, 10304, 11328, 11344, 12288, 13312),
+    (64, 128, 16): (8192, 8320, 10368, 10384, 12288, 14336),
+    (96, 128, 16): (12288, 12416, 14464, 14480, 16384, 18432),
+    (224, 128, 32): (28672, 28800, 32896, 32928, 32768, 36864),   # header
+    (32, 256, 32): (8192, 8448, 16640, 16672, 16384, 24576),
+    (64, 256, 16): (16384, 16640, 20736, 20752, 24576, 28672),
+    (96, 256, 16): (24576, 24832, 28928, 28944, 32768, 36864),   # header
+}
+
+
+def test_geometry_matches_the_host_header():
+    """Every geometry tests/oracle64.py runs gives, through
+    reference.Geometry, the literal numbers above, four lines of which the
+    header's GenGeometry is asserted to give at compile time."""
+    import oracle64 as o64
+
+    shapes = [s for _, s in o64.STEP_INSTANTIATIONS + o64.PRED_INSTANTIATIONS]
+    shapes += [s for s, _ in o64.E2E_CASES] + [o64.SPEC_SHAPE]
+    shapes += [s for _, s in o64.ADAM_KERNELS]
+    seen = set()
+    for shape in shapes:
+        g = Geometry(*shape)
+        seen.add((g.inp, g.hid, g.cpad))
+        want = HOST_GEOMETRY_LITERALS[(g.inp, g.hid, g.cpad)]
+        o2 = g.hid * g.inp + g.hid * 32
+        assert (g.off_b1, g.off_w2, g.off_b2, g.nparam, o2, g.wimg_n) == want, shape
+        assert g.off_w1 == 0 and g.slab_stride >= g.nparam + 2
+    assert seen == set(HOST_GEOMETRY_LITERALS)
+
+
+@pytest.mark.parametrize("hid,cpad,batch,want", [
+    # (hid, cpad) -> the old per-width table {32: (128, 64), 64: (128, 64),
+    # 128: (64, 32), 256: (32, 32)} = (big, small): small up to 128
+    # workgroups of it, big beyond; cpad 32 always big
+    (32, 16, 64 * 128, 64), (32, 16, 64 * 128 + 1, 128),
+    (64, 16, 64 * 128, 64), (64, 16, 64 * 128 + 1, 128),
+    (128, 16, 32 * 128, 32), (128, 16, 32 * 128 + 1, 64),
+    (256, 16, 32 * 128, 32), (256, 16, 32 * 128 + 1, 32),
+    (32, 32, 128 * 128, 128), (32, 32, 128 * 128 + 1, 128),
+    (64, 32, 128 * 128, 128), (64, 32, 128 * 128 + 1, 128),
+    (128, 32, 64 * 128, 64), (128, 32, 64 * 128 + 1, 64),
+    (256, 32, 32 * 128, 32), (256, 32, 32 * 128 + 1, 32),
+])
+def test_rows_per_wg(hid, cpad, batch, want):
+    """TabularMLP._rows_per_wg on both sides of the 128-workgroup threshold
+    for every compiled (hid, cpad), both heads."""
+    from unionml_amd.ops.tabular import TabularMLPRegressor
+
+    clf = TabularMLP(20, hid - 3, 2 if cpad == 16 else 17, device="cpu")
+    reg = TabularMLPRegressor(20, hid - 3, 1 if cpad == 16 else 17, device="cpu")
+    for model in (clf, reg):
+        assert (model.g.hid, model.g.cpad) == (hid, cpad)
+        assert model._rows_per_wg(batch) == want
+        assert model._rows_per_wg(1) == ref.compiled_rts(hid, cpad)[0]
+        assert model._rows_per_wg() == ref.compiled_rts(hid, cpad)[-1]
+    assert TabularMLP(device="cpu")._rows_per_wg(batch) == 128

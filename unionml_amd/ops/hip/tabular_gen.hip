@@ -885,20 +885,12 @@ int launch_step_gen_t(const unsigned short* Xbf, const head_target_t<HEAD>* y,
                       const float* master, float* slabs, int slab_stride,
                       int max_slabs, float invBtot, hipStream_t stream) {
   using G = gen::GG<HID, RT, CP>;
+  constexpr auto kernel = gen::mlp_step_gen_kernel<HID, RT, CP, HEAD>;
   const int blocks = (B + RT - 1) / RT;
   if (blocks > max_slabs) return -1;
-  static int done = 0;
-  if (!done) {
-    if (hipFuncSetAttribute(
-            (const void*)gen::mlp_step_gen_kernel<HID, RT, CP, HEAD>,
-            hipFuncAttributeMaxDynamicSharedMemorySize, G::TOTAL) != hipSuccess) {
-      return -2;
-    }
-    done = 1;
-  }
-  hipLaunchKernelGGL((gen::mlp_step_gen_kernel<HID, RT, CP, HEAD>), dim3(blocks),
-                     dim3(G::BLOCK), G::TOTAL, stream, Xbf, y, B, inp, cls, wimg,
-                     master, slabs, slab_stride, invBtot);
+  if (ensure_dynamic_lds<kernel>(G::TOTAL) != 0) return -2;
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(G::BLOCK), G::TOTAL, stream, Xbf,
+                     y, B, inp, cls, wimg, master, slabs, slab_stride, invBtot);
   return 0;
 }
 
@@ -909,20 +901,60 @@ int launch_predict_gen_t(const float* X, int B, int draw, int inp, int cls,
                          typename gen::predict_aux<HEAD>::type aux, float* out,
                          hipStream_t stream) {
   using G = gen::GG<HID, RT, CP>;
-  static int done = 0;
-  if (!done) {
-    if (hipFuncSetAttribute(
-            (const void*)gen::mlp_predict_gen_kernel<HID, RT, CP, HEAD>,
-            hipFuncAttributeMaxDynamicSharedMemorySize, G::TOTAL) != hipSuccess) {
-      return -2;
-    }
-    done = 1;
-  }
+  constexpr auto kernel = gen::mlp_predict_gen_kernel<HID, RT, CP, HEAD>;
+  if (ensure_dynamic_lds<kernel>(G::TOTAL) != 0) return -2;
   const int blocks = (B + RT - 1) / RT;
-  hipLaunchKernelGGL((gen::mlp_predict_gen_kernel<HID, RT, CP, HEAD>),
-                     dim3(blocks), dim3(G::BLOCK), G::TOTAL, stream, X, B, draw,
-                     inp, cls, mean, invstd, wimg, master, aux, out);
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(G::BLOCK), G::TOTAL, stream, X, B,
+                     draw, inp, cls, mean, invstd, wimg, master, aux, out);
   return 0;
+}
+
+// what both dispatchers refuse before they look at the table; n_out is the
+// head's class or target count
+bool gen_args_ok(int B, int inp, int hid, int n_out) {
+  return B >= 1 && n_out >= 1 && n_out <= 32 &&
+         GenGeometry{inp, hid, GenGeometry::cpad_for(n_out)}.ok();
+}
+
+// The two dispatchers are the only users of TABULAR_GEN_INSTANTIATIONS and
+// the only callers of launch_*_gen_t: a kernel is compiled if and only if
+// the table has its row.
+template <int HEAD>
+int dispatch_step_gen(const unsigned short* Xbf, const head_target_t<HEAD>* y,
+                      int B, int inp, int hid, int n_out, int rt,
+                      const unsigned short* wimg, const float* master,
+                      float* slabs, int slab_stride, int max_slabs,
+                      float invBtot, hipStream_t stream) {
+  if (!gen_args_ok(B, inp, hid, n_out)) return -3;
+  const int cpad = GenGeometry::cpad_for(n_out);
+  #define STEP_ROW(H, R, C, PREDICT)                                          \
+    if (hid == H && rt == R && cpad == C)                                     \
+      return launch_step_gen_t<H, R, C, HEAD>(Xbf, y, B, inp, n_out, wimg,    \
+                                              master, slabs, slab_stride,     \
+                                              max_slabs, invBtot, stream);
+  TABULAR_GEN_INSTANTIATIONS(STEP_ROW)
+  #undef STEP_ROW
+  return -3;
+}
+
+template <int HEAD>
+int dispatch_predict_gen(const float* X, int B, int draw, int inp, int hid,
+                         int n_out, const float* mean, const float* invstd,
+                         const unsigned short* wimg, const float* master,
+                         typename gen::predict_aux<HEAD>::type aux, float* out,
+                         hipStream_t stream) {
+  if (!gen_args_ok(B, inp, hid, n_out) || draw < 1 || draw > inp) return -3;
+  const int cpad = GenGeometry::cpad_for(n_out);
+  #define PREDICT_ROW(H, R, C, PREDICT)                                       \
+    if constexpr (PREDICT) {                                                  \
+      if (hid == H && cpad == C)                                              \
+        return launch_predict_gen_t<H, R, C, HEAD>(X, B, draw, inp, n_out,    \
+                                                   mean, invstd, wimg, master, \
+                                                   aux, out, stream);         \
+    }
+  TABULAR_GEN_INSTANTIATIONS(PREDICT_ROW)
+  #undef PREDICT_ROW
+  return -3;
 }
 
 }  // namespace
@@ -933,118 +965,60 @@ int launch_mlp_step_gen(const unsigned short* Xbf, const int* y, int B, int inp,
                         int hid, int cls, int rt, const unsigned short* wimg,
                         const float* master, float* slabs, int slab_stride,
                         int max_slabs, float invBtot, hipStream_t stream) {
-  if (inp % 32 != 0 || cls > 32) return -3;
-  #define STEP_CASE(H, R, C)                                                  \
-    if (hid == H && rt == R && cls <= C && (C == 16 ? cls <= 16 : cls > 16))  \
-      return launch_step_gen_t<H, R, C, HEAD_XENT>(                           \
-          Xbf, y, B, inp, cls, wimg, master, slabs, slab_stride, max_slabs,   \
-          invBtot, stream);
-  STEP_CASE(32, 128, 16)
-  STEP_CASE(32, 64, 16)
-  STEP_CASE(64, 128, 16)
-  STEP_CASE(64, 64, 16)
-  STEP_CASE(128, 64, 16)
-  STEP_CASE(128, 32, 16)
-  STEP_CASE(256, 32, 16)
-  STEP_CASE(32, 128, 32)
-  STEP_CASE(64, 128, 32)
-  STEP_CASE(128, 64, 32)
-  STEP_CASE(256, 32, 32)
-  #undef STEP_CASE
-  return -3;
+  return dispatch_step_gen<HEAD_XENT>(Xbf, y, B, inp, hid, cls, rt, wimg, master,
+                                      slabs, slab_stride, max_slabs, invBtot,
+                                      stream);
 }
 
-// regression head: the same <HID, RT, CPAD> list as STEP_CASE above, one
-// for one (a regressor has no specialized kernels: every shape lands here)
+// a regressor has no specialized kernels: every shape lands here
 int launch_mlp_step_reg_gen(const unsigned short* Xbf, const float* Yt, int B,
                             int inp, int hid, int targets, int rt,
                             const unsigned short* wimg, const float* master,
                             float* slabs, int slab_stride, int max_slabs,
                             float invBtot, hipStream_t stream) {
-  if (inp % 32 != 0 || targets < 1 || targets > 32 || B < 1) return -3;
-  #define STEP_REG_CASE(H, R, C)                                              \
-    if (hid == H && rt == R && (C == 16 ? targets <= 16 : targets > 16))      \
-      return launch_step_gen_t<H, R, C, HEAD_REG>(                            \
-          Xbf, Yt, B, inp, targets, wimg, master, slabs, slab_stride,         \
-          max_slabs, invBtot, stream);
-  STEP_REG_CASE(32, 128, 16)
-  STEP_REG_CASE(32, 64, 16)
-  STEP_REG_CASE(64, 128, 16)
-  STEP_REG_CASE(64, 64, 16)
-  STEP_REG_CASE(128, 64, 16)
-  STEP_REG_CASE(128, 32, 16)
-  STEP_REG_CASE(256, 32, 16)
-  STEP_REG_CASE(32, 128, 32)
-  STEP_REG_CASE(64, 128, 32)
-  STEP_REG_CASE(128, 64, 32)
-  STEP_REG_CASE(256, 32, 32)
-  #undef STEP_REG_CASE
-  return -3;
+  return dispatch_step_gen<HEAD_REG>(Xbf, Yt, B, inp, hid, targets, rt, wimg,
+                                     master, slabs, slab_stride, max_slabs,
+                                     invBtot, stream);
 }
 
-void launch_reduce_adam_gen(const float* slabs, int n_wg, int slab_stride,
-                            int inp, int hid, int cpad, float* master,
-                            unsigned short* bfmirror, float* m, float* v,
-                            int* t_dev, float* loss_out, float lr, float beta1,
-                            float beta2, float eps, unsigned short* wimg,
-                            float* grads_out, unsigned* done_counter,
-                            hipStream_t stream) {
-  const int nparam = inp * hid + hid + hid * cpad + cpad;
+int launch_reduce_adam_gen(const float* slabs, int n_wg, int slab_stride,
+                           int inp, int hid, int cpad, float* master,
+                           unsigned short* bfmirror, float* m, float* v,
+                           int* t_dev, float* loss_out, float lr, float beta1,
+                           float beta2, float eps, unsigned short* wimg,
+                           float* grads_out, unsigned* done_counter,
+                           hipStream_t stream) {
+  const GenGeometry g{inp, hid, cpad};
+  if (!g.ok() || n_wg < 1 || slab_stride < g.min_slab_stride()) return -3;
+  const int nparam = (int)g.nparam();
   int blocks = (nparam + 255) / 256;
   if (blocks > 512) blocks = 512;
   hipLaunchKernelGGL(gen::reduce_adam_gen_kernel, dim3(blocks), dim3(256), 0,
                      stream, slabs, n_wg, slab_stride, nparam, inp, hid, cpad,
                      master, bfmirror, m, v, t_dev, loss_out, lr, beta1, beta2,
                      eps, wimg, grads_out, done_counter);
+  return 0;
 }
 
 int launch_mlp_predict_gen(const float* X, int B, int draw, int inp, int hid,
                            int cls, const float* mean, const float* invstd,
                            const unsigned short* wimg, const float* master,
                            int* preds, float* probs, hipStream_t stream) {
-  if (inp % 32 != 0 || cls > 32) return -3;
-  #define PRED_CASE(H, R, C)                                                  \
-    if (hid == H && (C == 16 ? cls <= 16 : cls > 16))                         \
-      return launch_predict_gen_t<H, R, C, HEAD_XENT>(                        \
-          X, B, draw, inp, cls, mean, invstd, wimg, master, preds, probs,     \
-          stream);
-  PRED_CASE(32, 128, 16)
-  PRED_CASE(64, 128, 16)
-  PRED_CASE(128, 64, 16)
-  PRED_CASE(256, 32, 16)
-  PRED_CASE(32, 128, 32)
-  PRED_CASE(64, 128, 32)
-  PRED_CASE(128, 64, 32)
-  PRED_CASE(256, 32, 32)
-  #undef PRED_CASE
-  return -3;
+  return dispatch_predict_gen<HEAD_XENT>(X, B, draw, inp, hid, cls, mean, invstd,
+                                         wimg, master, preds, probs, stream);
 }
 
-// regression head: the same <HID, RT, CPAD> list as PRED_CASE above
 int launch_mlp_predict_reg_gen(const float* X, int B, int draw, int inp, int hid,
                                int targets, const float* mean,
                                const float* invstd, const unsigned short* wimg,
                                const float* master, const float* y_mean,
                                const float* y_scale, float* out, int ldo,
                                hipStream_t stream) {
-  if (inp % 32 != 0 || targets < 1 || targets > 32 || ldo < targets || B < 1) {
-    return -3;
-  }
-  #define PRED_REG_CASE(H, R, C)                                              \
-    if (hid == H && (C == 16 ? targets <= 16 : targets > 16))                 \
-      return launch_predict_gen_t<H, R, C, HEAD_REG>(                         \
-          X, B, draw, inp, targets, mean, invstd, wimg, master,               \
-          gen::RegAffine{y_mean, y_scale, ldo}, out, stream);
-  PRED_REG_CASE(32, 128, 16)
-  PRED_REG_CASE(64, 128, 16)
-  PRED_REG_CASE(128, 64, 16)
-  PRED_REG_CASE(256, 32, 16)
-  PRED_REG_CASE(32, 128, 32)
-  PRED_REG_CASE(64, 128, 32)
-  PRED_REG_CASE(128, 64, 32)
-  PRED_REG_CASE(256, 32, 32)
-  #undef PRED_REG_CASE
-  return -3;
+  if (ldo < targets) return -3;
+  return dispatch_predict_gen<HEAD_REG>(X, B, draw, inp, hid, targets, mean,
+                                        invstd, wimg, master,
+                                        gen::RegAffine{y_mean, y_scale, ldo}, out,
+                                        stream);
 }
 
 void launch_adam_step_gen(float* master, unsigned short* bfmirror,

@@ -1341,11 +1341,6 @@ reduce_selftest_kernel(const float* __restrict__ x, int n,
 // host launchers (extern "C"; stream-ordered, capture-safe)
 // ---------------------------------------------------------------------------
 
-static int set_lds(const void* kernel, int bytes) {
-  return (int)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  bytes);
-}
-
 extern "C" {
 
 void launch_standardize_fit(const float* X, long long N, int D, float* mean,
@@ -1384,15 +1379,16 @@ void launch_standardize_apply(const float* X, long long N, int D, int Dout,
                      X, n, D, Dout, mean, invstd, out);
 }
 
-void launch_mlp_step(const unsigned short* Xbf, const int* y, int B,
-                     const unsigned short* W1bf, const unsigned short* W2bf,
-                     const float* master, float* grads, float invBtot,
-                     hipStream_t stream) {
-  static int done = 0;
-  if (!done) { set_lds((const void*)mlp_step_kernel, C_IMG_TOTAL); done = 1; }
+int launch_mlp_step(const unsigned short* Xbf, const int* y, int B,
+                    const unsigned short* W1bf, const unsigned short* W2bf,
+                    const float* master, float* grads, float invBtot,
+                    hipStream_t stream) {
+  if (B < 1) return -3;
+  if (ensure_dynamic_lds<mlp_step_kernel>(C_IMG_TOTAL) != 0) return -2;
   const int blocks = (B + ROWS - 1) / ROWS;
   hipLaunchKernelGGL(mlp_step_kernel, dim3(blocks), dim3(BLOCK), C_IMG_TOTAL,
                      stream, Xbf, y, B, W1bf, W2bf, master, grads, invBtot);
+  return 0;
 }
 
 int launch_mlp_step_fused(const unsigned short* Xbf, const int* y, int B,
@@ -1402,13 +1398,10 @@ int launch_mlp_step_fused(const unsigned short* Xbf, const int* y, int B,
                           float* loss_out, float invBtot, float lr, float beta1,
                           float beta2, float eps, int max_slabs, float* grads_out,
                           unsigned short* wimg, hipStream_t stream) {
+  if (B < 1) return -3;
   const int blocks = (B + ROWS - 1) / ROWS;
   if (blocks > max_slabs) return -1;
-  static int done = 0;
-  if (!done) {
-    if (set_lds((const void*)mlp_step_fused_kernel, C_IMG_TOTAL) != 0) return -2;
-    done = 1;
-  }
+  if (ensure_dynamic_lds<mlp_step_fused_kernel>(C_IMG_TOTAL) != 0) return -2;
   hipLaunchKernelGGL(mlp_step_fused_kernel, dim3(blocks), dim3(BLOCK), C_IMG_TOTAL,
                      stream, Xbf, y, B, wimg, master, counter, t_dev, W1bf, W2bf,
                      bfmirror, m, v, slabs, loss_out, invBtot, lr, beta1, beta2, eps,
@@ -1421,27 +1414,25 @@ int launch_mlp_train_steps(const unsigned short* Xbf, const int* y, long long N,
                            unsigned short* bfmirror, float* m, float* v,
                            int* t_dev, float* loss_out, float lr, float beta1,
                            float beta2, float eps, hipStream_t stream) {
-  if (B % ROWS != 0 || N % B != 0) return -1;   // caller falls back
-  static int done = 0;
-  if (!done) {
-    if (set_lds((const void*)mlp_train_steps_kernel, C_STEPS_TOTAL) != 0) return -2;
-    done = 1;
-  }
+  if (B < 1 || N < 1 || n_steps < 0) return -3;   // before N % B divides
+  if (B % ROWS != 0 || N % B != 0) return -1;     // caller falls back
+  if (ensure_dynamic_lds<mlp_train_steps_kernel>(C_STEPS_TOTAL) != 0) return -2;
   hipLaunchKernelGGL(mlp_train_steps_kernel, dim3(1), dim3(BLOCK), C_STEPS_TOTAL,
                      stream, Xbf, y, N, B, n_steps, master, bfmirror, m, v,
                      t_dev, loss_out, lr, beta1, beta2, eps);
   return 0;
 }
 
-void launch_mlp_predict(const float* X, int B, const float* mean,
-                        const float* invstd, const unsigned short* W1bf,
-                        const unsigned short* W2bf, const float* master,
-                        int* preds, float* probs, hipStream_t stream) {
-  static int done = 0;
-  if (!done) { set_lds((const void*)mlp_predict_kernel, C_IMG_TOTAL); done = 1; }
+int launch_mlp_predict(const float* X, int B, const float* mean,
+                       const float* invstd, const unsigned short* W1bf,
+                       const unsigned short* W2bf, const float* master,
+                       int* preds, float* probs, hipStream_t stream) {
+  if (B < 1) return -3;
+  if (ensure_dynamic_lds<mlp_predict_kernel>(C_IMG_TOTAL) != 0) return -2;
   const int blocks = (B + ROWS - 1) / ROWS;
   hipLaunchKernelGGL(mlp_predict_kernel, dim3(blocks), dim3(BLOCK), C_IMG_TOTAL,
                      stream, X, B, mean, invstd, W1bf, W2bf, master, preds, probs);
+  return 0;
 }
 
 void launch_adam_step(float* master, unsigned short* bfmirror, const float* grads,

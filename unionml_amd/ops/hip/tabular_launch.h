@@ -1,13 +1,16 @@
 // Host-visible interface of the tabular kernels: the digits-geometry
-// layout constants and every extern "C" launcher, declared ONCE. Both
-// kernel files and the torch bindings include this header, so a launcher
-// whose definition drifts from its declaration is a compile error instead
-// of a silently mis-ordered argument list.
+// layout constants, the generalized kernels' instantiation table and padded
+// geometry, and every extern "C" launcher, declared ONCE. Both kernel files
+// and the torch bindings include this header, so a launcher whose
+// definition drifts from its declaration is a compile error instead of a
+// silently mis-ordered argument list.
 //
 // The constants carry a DIGITS_ prefix: short names such as IN or HID
 // clash with macros of other headers and with the generalized kernels'
 // template parameters.
 #pragma once
+
+#include <climits>
 
 #include <hip/hip_runtime_api.h>
 
@@ -46,6 +49,100 @@ static_assert(DIGITS_NPARAM == 2608 && DIGITS_SLAB == 2624 &&
                   DIGITS_WIMG_N == 4224,
               "digits layout changed: staged buffers and checkpoints depend on it");
 
+// ---- generalized kernels (tabular_gen.hip): table and geometry ---------------
+
+// Every compiled <HID, RT, CPAD> instantiation of the generalized step
+// kernel, one row each, for both heads. PREDICT marks the row whose RT the
+// predict kernel is compiled at too: the larger RT of its (HID, CPAD). The
+// step dispatch matches (hid, rt, cpad) exactly, the predict dispatch
+// (hid, cpad). ops/reference.py GEN_INSTANTIATIONS is the Python copy; a
+// test holds the two equal.
+//   X(HID, RT, CPAD, PREDICT)
+#define TABULAR_GEN_INSTANTIATIONS(X) \
+  X(32, 128, 16, 1)                   \
+  X(32, 64, 16, 0)                    \
+  X(64, 128, 16, 1)                   \
+  X(64, 64, 16, 0)                    \
+  X(128, 64, 16, 1)                   \
+  X(128, 32, 16, 0)                   \
+  X(256, 32, 16, 1)                   \
+  X(32, 128, 32, 1)                   \
+  X(64, 128, 32, 1)                   \
+  X(128, 64, 32, 1)                   \
+  X(256, 32, 32, 1)
+
+// Padded geometry of the generalized kernels as the host sees it (the
+// Python copy is reference.Geometry): the flat master/grads layout
+//   W1 [inp][hid] | b1 [hid] | W2 [hid][cpad] | b2 [cpad] | loss (grads only)
+// and the packed weight image W1T [hid][inp] | W2s [hid][32] | W2T [cpad][hid].
+// Sizes are 64-bit here; the kernels index with int, so ok() refuses a
+// geometry whose slab row or image does not fit one.
+struct GenGeometry {
+  long long inp, hid, cpad;   // staged input width, compiled hidden, padded outputs
+
+  // classes or targets (1..32) padded to one or two MFMA tiles
+  static constexpr int cpad_for(long long n_out) { return n_out <= 16 ? 16 : 32; }
+
+  constexpr long long off_w1() const { return 0; }
+  constexpr long long off_b1() const { return inp * hid; }
+  constexpr long long off_w2() const { return off_b1() + hid; }
+  constexpr long long off_b2() const { return off_w2() + hid * cpad; }
+  constexpr long long nparam() const { return off_b2() + cpad; }
+  // a workgroup's slab row: nparam + loss + epoch tag
+  constexpr long long min_slab_stride() const { return nparam() + 2; }
+  constexpr long long wimg_w2s() const { return hid * inp; }
+  constexpr long long wimg_w2t() const { return wimg_w2s() + hid * 32; }
+  constexpr long long wimg_n() const { return wimg_w2t() + cpad * hid; }
+
+  constexpr bool ok() const {
+    return inp >= 32 && inp % 32 == 0 && inp <= INT_MAX && hid >= 1 &&
+           hid <= INT_MAX && (cpad == 16 || cpad == 32) &&
+           min_slab_stride() <= INT_MAX && wimg_n() <= INT_MAX;
+  }
+};
+
+constexpr GenGeometry DIGITS_AS_GEN{DIGITS_IN, DIGITS_HID, DIGITS_CPAD};
+static_assert(DIGITS_AS_GEN.ok() && DIGITS_AS_GEN.off_b1() == DIGITS_OFF_B1 &&
+                  DIGITS_AS_GEN.off_w2() == DIGITS_OFF_W2 &&
+                  DIGITS_AS_GEN.off_b2() == DIGITS_OFF_B2 &&
+                  DIGITS_AS_GEN.nparam() == DIGITS_NPARAM,
+              "the digits flat layout is the generalized one at 64x32x16");
+// four of the geometries tests/oracle64.py runs, as reference.Geometry
+// computes them (tests/test_tabular_gen_cpu.py holds Geometry to the same
+// literals and to the rest of the set):
+//   {inp, hid, cpad} -> off_b1, off_w2, off_b2, nparam, image W2T offset, size
+constexpr bool gen_geometry_is(GenGeometry g, long long off_b1, long long off_w2,
+                               long long off_b2, long long nparam,
+                               long long wimg_w2t, long long wimg_n) {
+  return g.ok() && g.off_b1() == off_b1 && g.off_w2() == off_w2 &&
+         g.off_b2() == off_b2 && g.nparam() == nparam &&
+         g.min_slab_stride() == nparam + 2 && g.wimg_w2s() == off_b1 &&
+         g.wimg_w2t() == wimg_w2t && g.wimg_n() == wimg_n;
+}
+static_assert(
+    gen_geometry_is({32, 32, 16}, 1024, 1056, 1568, 1584, 2048, 2560) &&
+        gen_geometry_is({32, 32, 32}, 1024, 1056, 2080, 2112, 2048, 3072) &&
+        gen_geometry_is({224, 128, 32}, 28672, 28800, 32896, 32928, 32768, 36864) &&
+        gen_geometry_is({96, 256, 16}, 24576, 24832, 28928, 28944, 32768, 36864),
+    "GenGeometry and reference.Geometry disagree");
+static_assert(!GenGeometry{1LL << 23, 256, 16}.ok() && !GenGeometry{48, 32, 16}.ok() &&
+                  !GenGeometry{32, 32, 24}.ok() && GenGeometry{1LL << 20, 256, 32}.ok(),
+              "ok() refuses what an int cannot index and unpadded widths");
+
+// Raise a kernel's dynamic-LDS limit to `bytes`: 0, or -2 when the runtime
+// refuses. Done once per process and kernel (the flag is per instantiation),
+// as the launchers always did; per-device setup is not attempted.
+template <auto Kernel>
+int ensure_dynamic_lds(int bytes) {
+  static bool done = false;
+  if (!done) {
+    done = hipFuncSetAttribute((const void*)Kernel,
+                               hipFuncAttributeMaxDynamicSharedMemorySize,
+                               bytes) == hipSuccess;
+  }
+  return done ? 0 : -2;
+}
+
 extern "C" {
 
 // ---- tabular_kernels.hip ---------------------------------------------------
@@ -56,11 +153,15 @@ void launch_standardize_fit(const float* X, long long N, int D, float* mean,
 void launch_standardize_apply(const float* X, long long N, int D, int Dout,
                               const float* mean, const float* invstd,
                               unsigned short* out, hipStream_t stream);
-void launch_mlp_step(const unsigned short* Xbf, const int* y, int B,
-                     const unsigned short* W1bf, const unsigned short* W2bf,
-                     const float* master, float* grads, float invBtot,
-                     hipStream_t stream);
-// -1: more workgroups than slab rows, -2: LDS attribute failed
+// Return codes of the int launchers: 0 launched; -2 the dynamic-LDS
+// attribute failed; -3 arguments outside what the kernels take (a batch
+// below one row, or, for the generalized family, no instantiation for the
+// geometry); -1 is per launcher, below.
+int launch_mlp_step(const unsigned short* Xbf, const int* y, int B,
+                    const unsigned short* W1bf, const unsigned short* W2bf,
+                    const float* master, float* grads, float invBtot,
+                    hipStream_t stream);
+// -1: more workgroups than slab rows
 int launch_mlp_step_fused(const unsigned short* Xbf, const int* y, int B,
                           const unsigned short* W1bf, const unsigned short* W2bf,
                           float* master, unsigned short* bfmirror, float* m,
@@ -68,16 +169,16 @@ int launch_mlp_step_fused(const unsigned short* Xbf, const int* y, int B,
                           float* loss_out, float invBtot, float lr, float beta1,
                           float beta2, float eps, int max_slabs, float* grads_out,
                           unsigned short* wimg, hipStream_t stream);
-// -1: shape constraints unmet (caller falls back), -2: LDS attribute failed
+// -1: shape constraints unmet (caller falls back)
 int launch_mlp_train_steps(const unsigned short* Xbf, const int* y, long long N,
                            int B, int n_steps, float* master,
                            unsigned short* bfmirror, float* m, float* v,
                            int* t_dev, float* loss_out, float lr, float beta1,
                            float beta2, float eps, hipStream_t stream);
-void launch_mlp_predict(const float* X, int B, const float* mean,
-                        const float* invstd, const unsigned short* W1bf,
-                        const unsigned short* W2bf, const float* master,
-                        int* preds, float* probs, hipStream_t stream);
+int launch_mlp_predict(const float* X, int B, const float* mean,
+                       const float* invstd, const unsigned short* W1bf,
+                       const unsigned short* W2bf, const float* master,
+                       int* preds, float* probs, hipStream_t stream);
 void launch_adam_step(float* master, unsigned short* bfmirror, const float* grads,
                       float* m, float* v, int* t_dev, float lr, float beta1,
                       float beta2, float eps, unsigned short* wimg,
@@ -89,19 +190,18 @@ void launch_reduce_selftest(const float* x, int n, float* out,
 
 // ---- tabular_gen.hip (any geometry) -----------------------------------------
 
-// -1: more workgroups than slab rows, -2: LDS attribute failed,
-// -3: no instantiation for the geometry
+// -1: more workgroups than slab rows
 int launch_mlp_step_gen(const unsigned short* Xbf, const int* y, int B, int inp,
                         int hid, int cls, int rt, const unsigned short* wimg,
                         const float* master, float* slabs, int slab_stride,
                         int max_slabs, float invBtot, hipStream_t stream);
-void launch_reduce_adam_gen(const float* slabs, int n_wg, int slab_stride,
-                            int inp, int hid, int cpad, float* master,
-                            unsigned short* bfmirror, float* m, float* v,
-                            int* t_dev, float* loss_out, float lr, float beta1,
-                            float beta2, float eps, unsigned short* wimg,
-                            float* grads_out, unsigned* done_counter,
-                            hipStream_t stream);
+int launch_reduce_adam_gen(const float* slabs, int n_wg, int slab_stride,
+                           int inp, int hid, int cpad, float* master,
+                           unsigned short* bfmirror, float* m, float* v,
+                           int* t_dev, float* loss_out, float lr, float beta1,
+                           float beta2, float eps, unsigned short* wimg,
+                           float* grads_out, unsigned* done_counter,
+                           hipStream_t stream);
 int launch_mlp_predict_gen(const float* X, int B, int draw, int inp, int hid,
                            int cls, const float* mean, const float* invstd,
                            const unsigned short* wimg, const float* master,

@@ -3,8 +3,6 @@
 // tabular_launch.h). All launches go to the current torch stream so they
 // compose with torch.cuda.graphs capture and RCCL work.
 
-#include <climits>
-
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
@@ -22,6 +20,35 @@ void check(const torch::Tensor& t, torch::ScalarType dtype, const char* name) {
   TORCH_CHECK(t.scalar_type() == dtype, name, " has wrong dtype");
 }
 
+// check() plus a least (or, with exact, the only) element count
+void check_n(const torch::Tensor& t, torch::ScalarType dtype, const char* name,
+             int64_t numel, bool exact = false) {
+  check(t, dtype, name);
+  TORCH_CHECK(exact ? t.numel() == numel : t.numel() >= numel, name, " must hold ",
+              exact ? "exactly " : "at least ", numel, " elements, has ", t.numel());
+}
+
+// the kernels load 16-byte vectors from these
+void check_aligned16(const torch::Tensor& t, const char* name) {
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, name,
+              " must be 16-byte aligned");
+}
+
+// a [B][cols] matrix, 1 <= B <= max_rows -> B (cols 0: any width 1..INT_MAX).
+// max_rows is INT_MAX where the launcher takes int B, INT64_MAX where it
+// takes long long N.
+int64_t check_rows(const torch::Tensor& t, torch::ScalarType dtype, const char* name,
+                   int64_t cols = 0, int64_t max_rows = INT_MAX) {
+  check(t, dtype, name);
+  TORCH_CHECK(t.dim() == 2 && t.size(0) >= 1 && t.size(0) <= max_rows &&
+                  t.size(1) >= 1 && t.size(1) <= INT_MAX &&
+                  (cols == 0 || t.size(1) == cols),
+              name, " must be [1 <= B <= ", max_rows, "][",
+              cols ? std::to_string(cols) : std::string("1 <= width <= INT_MAX"),
+              "], is ", t.sizes());
+  return t.size(0);
+}
+
 const unsigned short* bf16_ptr(const torch::Tensor& t) {
   return reinterpret_cast<const unsigned short*>(t.data_ptr());
 }
@@ -35,17 +62,66 @@ template <typename T>
 T* opt_ptr(const c10::optional<torch::Tensor>& t, torch::ScalarType dtype,
            const char* name, int64_t min_numel = 0) {
   if (!t.has_value()) return nullptr;
-  check(*t, dtype, name);
-  TORCH_CHECK(t->numel() >= min_numel, name, " too small: needs ", min_numel,
-              " elements");
+  check_n(*t, dtype, name, min_numel);
   return reinterpret_cast<T*>(t->data_ptr());
 }
+
+// optional class probabilities [>= B][cls], dense
+float* probs_ptr(const c10::optional<torch::Tensor>& probs, int B, int64_t cls) {
+  TORCH_CHECK(!probs.has_value() || (probs->dim() == 2 && probs->size(0) >= B &&
+                                     probs->size(1) == cls),
+              "probs must be [>= ", B, "][", cls, "]");
+  return opt_ptr<float>(probs, torch::kFloat32, "probs");
+}
+
+// feature standardizer of a raw [N][D] matrix
+void check_scaler(const torch::Tensor& mean, const torch::Tensor& invstd, int64_t D) {
+  check_n(mean, torch::kFloat32, "mean", D, true);
+  check_n(invstd, torch::kFloat32, "invstd", D, true);
+}
+
+// gradient slabs [n][stride >= min_stride] (exact: the digits stride)
+void check_slabs(const torch::Tensor& slabs, int64_t min_stride, bool exact = false) {
+  check(slabs, torch::kFloat32, "slabs");
+  TORCH_CHECK(slabs.dim() == 2 && slabs.size(0) <= INT_MAX &&
+                  slabs.size(1) <= INT_MAX &&
+                  (exact ? slabs.size(1) == min_stride : slabs.size(1) >= min_stride),
+              "slabs must be [n][", exact ? "" : ">= ", min_stride, "], is ",
+              slabs.sizes());
+}
+
+// ---- the digits state --------------------------------------------------------
 
 // the specialized kernels' packed weight image has one fixed size
 unsigned short* digits_wimg_ptr(const c10::optional<torch::Tensor>& wimg) {
   TORCH_CHECK(!wimg.has_value() || wimg->numel() == DIGITS_WIMG_N,
               "wimg must be the packed ", DIGITS_WIMG_N, "-elem image buffer");
+  if (wimg.has_value()) check_aligned16(*wimg, "wimg");
   return opt_ptr<unsigned short>(wimg, torch::kBFloat16, "wimg");
+}
+
+// a staged digits batch: Xbf [B][64] bf16 and one int32 label per row -> B
+int64_t digits_batch(const torch::Tensor& Xbf, const torch::Tensor& y,
+                     int64_t max_rows = INT_MAX) {
+  const int64_t B = check_rows(Xbf, torch::kBFloat16, "Xbf", DIGITS_IN, max_rows);
+  check_aligned16(Xbf, "Xbf");
+  check_n(y, torch::kInt32, "y", B, true);
+  return B;
+}
+
+// the bf16 weight views and the fp32 master every specialized kernel reads
+void digits_weights(const torch::Tensor& W1bf, const torch::Tensor& W2bf,
+                    const torch::Tensor& master) {
+  check_n(W1bf, torch::kBFloat16, "W1bf", DIGITS_IN * DIGITS_HID, true);
+  check_n(W2bf, torch::kBFloat16, "W2bf", DIGITS_HID * DIGITS_CPAD, true);
+  check_n(master, torch::kFloat32, "master", DIGITS_NPARAM);
+}
+
+// what a specialized launcher returned -> the binding's result
+bool digits_launched(int rc, const char* fn) {
+  TORCH_CHECK(rc != -2, fn, ": hipFuncSetAttribute(LDS) failed");
+  TORCH_CHECK(rc != -3, fn, ": arguments outside the kernel's range");
+  return rc == 0;   // false (-1): the caller re-sizes or falls back
 }
 
 // Adam state as every optimizer entry point takes it
@@ -60,32 +136,92 @@ struct AdamState {
 AdamState adam_state(const torch::Tensor& master, const torch::Tensor& bfmirror,
                      const torch::Tensor& m, const torch::Tensor& v,
                      const torch::Tensor& t_dev, int64_t nparam) {
-  check(master, torch::kFloat32, "master");
-  check(bfmirror, torch::kBFloat16, "bfmirror");
-  check(m, torch::kFloat32, "m");
-  check(v, torch::kFloat32, "v");
-  check(t_dev, torch::kInt32, "t_dev");
-  TORCH_CHECK(master.numel() >= nparam && bfmirror.numel() >= nparam &&
-                  m.numel() >= nparam && v.numel() >= nparam && t_dev.numel() >= 1,
-              "Adam state too small: master/bfmirror/m/v need ", nparam,
-              " elements, t_dev one");
+  check_n(master, torch::kFloat32, "master", nparam);
+  check_n(bfmirror, torch::kBFloat16, "bfmirror", nparam);
+  check_n(m, torch::kFloat32, "m", nparam);
+  check_n(v, torch::kFloat32, "v", nparam);
+  check_n(t_dev, torch::kInt32, "t_dev", 1);
   return {master.data_ptr<float>(), bf16_mut_ptr(bfmirror), m.data_ptr<float>(),
           v.data_ptr<float>(), t_dev.data_ptr<int>()};
 }
 
-int gen_nparam(int64_t inp, int64_t hid, int64_t cpad) {
-  return (int)(inp * hid + hid + hid * cpad + cpad);
+// ---- the generalized family ----------------------------------------------------
+
+// the padded geometry (inp, hid, cpad), refused when the kernels could not
+// index it; gen_geometry_for: the same from n_out classes or targets
+GenGeometry gen_geometry(int64_t inp, int64_t hid, int64_t cpad) {
+  TORCH_CHECK(cpad == 16 || cpad == 32, "cpad must be 16 or 32");
+  const GenGeometry g{inp, hid, cpad};
+  TORCH_CHECK(g.ok(), "unsupported geometry: inp=", inp, " must be a positive ",
+              "multiple of 32, hid=", hid, " positive, and nparam and the weight ",
+              "image must fit an int");
+  return g;
+}
+
+GenGeometry gen_geometry_for(int64_t inp, int64_t hid, int64_t n_out,
+                             const char* what) {
+  TORCH_CHECK(n_out >= 1 && n_out <= 32, what, " must be 1..32");
+  return gen_geometry(inp, hid, GenGeometry::cpad_for(n_out));
+}
+
+// the packed image and the master the step and the predict kernels read
+void gen_weights(const GenGeometry& g, const torch::Tensor& wimg,
+                 const torch::Tensor& master) {
+  check_n(wimg, torch::kBFloat16, "wimg", g.wimg_n());
+  check_aligned16(wimg, "wimg");
+  check_n(master, torch::kFloat32, "master", g.nparam());
+}
+
+// what the two helpers below return: the call's geometry and batch rows
+struct GenCall {
+  GenGeometry g;
+  int B;
+};
+
+// A generalized step's arguments, either head: all but the per-row targets,
+// which the head's binding holds to B.
+GenCall gen_step_args(const torch::Tensor& Xbf, int64_t hid, int64_t n_out,
+                      const char* n_out_name, int64_t rt,
+                      const torch::Tensor& wimg, const torch::Tensor& master,
+                      const torch::Tensor& slabs) {
+  const int B = (int)check_rows(Xbf, torch::kBFloat16, "Xbf");
+  check_aligned16(Xbf, "Xbf");
+  const GenGeometry g = gen_geometry_for(Xbf.size(1), hid, n_out, n_out_name);
+  TORCH_CHECK(rt >= 1 && rt <= INT_MAX, "rt must be a compiled rows-per-workgroup");
+  gen_weights(g, wimg, master);
+  check_slabs(slabs, g.min_slab_stride());
+  return {g, B};
+}
+
+// what a generalized launcher returned -> the binding's result
+bool gen_launched(int rc, const char* fn, const GenCall& a, int64_t n_out,
+                  int64_t rt = 0) {
+  TORCH_CHECK(rc != -2, fn, ": hipFuncSetAttribute(LDS) failed");
+  TORCH_CHECK(rc != -3, fn, ": unsupported geometry (hid=", a.g.hid,
+              " inp=", a.g.inp, " outputs=", n_out, " rt=", rt, ")");
+  return rc == 0;  // false -> more WGs than slab rows, caller re-sizes
+}
+
+// A generalized predict's arguments, either head: all but the outputs.
+GenCall gen_predict_args(const torch::Tensor& X, int64_t inp, int64_t hid,
+                         int64_t n_out, const char* n_out_name,
+                         const torch::Tensor& mean, const torch::Tensor& invstd,
+                         const torch::Tensor& wimg, const torch::Tensor& master) {
+  const int B = (int)check_rows(X, torch::kFloat32, "X");
+  const GenGeometry g = gen_geometry_for(inp, hid, n_out, n_out_name);
+  TORCH_CHECK(X.size(1) <= inp, "X must be [B][<= inp=", inp, "], is ", X.sizes());
+  check_scaler(mean, invstd, X.size(1));
+  gen_weights(g, wimg, master);
+  return {g, B};
 }
 
 }  // namespace
 
 void standardize_fit(torch::Tensor X, torch::Tensor mean, torch::Tensor invstd,
                      double eps) {
-  check(X, torch::kFloat32, "X");
-  check(mean, torch::kFloat32, "mean");
-  check(invstd, torch::kFloat32, "invstd");
+  check_rows(X, torch::kFloat32, "X", 0, INT64_MAX);   // long long N below
   const int D = (int)X.size(1);
-  TORCH_CHECK(mean.numel() == D && invstd.numel() == D, "mean/invstd size mismatch");
+  check_scaler(mean, invstd, D);
   double* scratch_ptr = nullptr;
   torch::Tensor scratch;
   if (D <= 256 && 256 % D == 0) {
@@ -99,10 +235,11 @@ void standardize_fit(torch::Tensor X, torch::Tensor mean, torch::Tensor invstd,
 
 void standardize_apply(torch::Tensor X, torch::Tensor mean, torch::Tensor invstd,
                        torch::Tensor out_bf16) {
-  check(X, torch::kFloat32, "X");
+  check_rows(X, torch::kFloat32, "X", 0, INT64_MAX);   // long long N below
+  check_scaler(mean, invstd, X.size(1));
   check(out_bf16, torch::kBFloat16, "out");
   TORCH_CHECK(out_bf16.dim() == 2 && out_bf16.size(0) == X.size(0) &&
-                  out_bf16.size(1) >= X.size(1),
+                  out_bf16.size(1) >= X.size(1) && out_bf16.size(1) <= INT_MAX,
               "out must be [N][Dout] with Dout >= D");
   launch_standardize_apply(X.data_ptr<float>(), X.size(0), (int)X.size(1),
                            (int)out_bf16.size(1), mean.data_ptr<float>(),
@@ -113,21 +250,14 @@ void standardize_apply(torch::Tensor X, torch::Tensor mean, torch::Tensor invstd
 void mlp_step(torch::Tensor Xbf, torch::Tensor y, torch::Tensor W1bf,
               torch::Tensor W2bf, torch::Tensor master, torch::Tensor grads,
               double invBtot) {
-  check(Xbf, torch::kBFloat16, "Xbf");
-  check(y, torch::kInt32, "y");
-  check(W1bf, torch::kBFloat16, "W1bf");
-  check(W2bf, torch::kBFloat16, "W2bf");
-  check(master, torch::kFloat32, "master");
-  check(grads, torch::kFloat32, "grads");
-  TORCH_CHECK(Xbf.size(1) == DIGITS_IN, "IN must be ", DIGITS_IN);
-  TORCH_CHECK(W1bf.numel() == DIGITS_IN * DIGITS_HID &&
-                  W2bf.numel() == DIGITS_HID * DIGITS_CPAD,
-              "weight shapes");
-  TORCH_CHECK(grads.numel() >= DIGITS_NPARAM + 1, "grads must hold ",
-              DIGITS_NPARAM, " params + loss");
-  launch_mlp_step(bf16_ptr(Xbf), y.data_ptr<int>(), (int)Xbf.size(0),
-                  bf16_ptr(W1bf), bf16_ptr(W2bf), master.data_ptr<float>(),
-                  grads.data_ptr<float>(), (float)invBtot, current_stream());
+  const int B = (int)digits_batch(Xbf, y);
+  digits_weights(W1bf, W2bf, master);
+  check_n(grads, torch::kFloat32, "grads", DIGITS_NPARAM + 1);
+  const int rc = launch_mlp_step(bf16_ptr(Xbf), y.data_ptr<int>(), B,
+                                 bf16_ptr(W1bf), bf16_ptr(W2bf),
+                                 master.data_ptr<float>(), grads.data_ptr<float>(),
+                                 (float)invBtot, current_stream());
+  digits_launched(rc, "mlp_step");
 }
 
 bool mlp_step_fused(torch::Tensor Xbf, torch::Tensor y, torch::Tensor W1bf,
@@ -138,25 +268,20 @@ bool mlp_step_fused(torch::Tensor Xbf, torch::Tensor y, torch::Tensor W1bf,
                     double beta1, double beta2, double eps,
                     c10::optional<torch::Tensor> grads_out = c10::nullopt,
                     c10::optional<torch::Tensor> wimg = c10::nullopt) {
-  check(Xbf, torch::kBFloat16, "Xbf");
-  check(y, torch::kInt32, "y");
+  const int B = (int)digits_batch(Xbf, y);
+  digits_weights(W1bf, W2bf, master);
   const AdamState st = adam_state(master, bfmirror, m, v, t_dev, DIGITS_NPARAM);
-  check(slabs, torch::kFloat32, "slabs");
-  check(counter, torch::kUInt32, "counter");
-  check(loss_out, torch::kFloat32, "loss_out");
-  TORCH_CHECK(Xbf.size(1) == DIGITS_IN, "IN must be ", DIGITS_IN);
-  TORCH_CHECK(slabs.dim() == 2 && slabs.size(1) == DIGITS_SLAB, "slabs must be [n][",
-              DIGITS_SLAB, "]");
+  check_slabs(slabs, DIGITS_SLAB, true);
+  check_n(counter, torch::kUInt32, "counter", 1);
+  check_n(loss_out, torch::kFloat32, "loss_out", 1);
   const int rc = launch_mlp_step_fused(
-      bf16_ptr(Xbf), y.data_ptr<int>(), (int)Xbf.size(0), bf16_ptr(W1bf),
-      bf16_ptr(W2bf), st.master, st.bfmirror, st.m, st.v, st.t_dev,
-      slabs.data_ptr<float>(), (unsigned*)counter.data_ptr(),
-      loss_out.data_ptr<float>(), (float)invBtot, (float)lr, (float)beta1,
-      (float)beta2, (float)eps, (int)slabs.size(0),
+      bf16_ptr(Xbf), y.data_ptr<int>(), B, bf16_ptr(W1bf), bf16_ptr(W2bf),
+      st.master, st.bfmirror, st.m, st.v, st.t_dev, slabs.data_ptr<float>(),
+      (unsigned*)counter.data_ptr(), loss_out.data_ptr<float>(), (float)invBtot,
+      (float)lr, (float)beta1, (float)beta2, (float)eps, (int)slabs.size(0),
       opt_ptr<float>(grads_out, torch::kFloat32, "grads_out", DIGITS_NPARAM + 1),
       digits_wimg_ptr(wimg), current_stream());
-  TORCH_CHECK(rc != -2, "mlp_step_fused: hipFuncSetAttribute(LDS) failed");
-  return rc == 0;
+  return digits_launched(rc, "mlp_step_fused");   // false: more WGs than slab rows
 }
 
 bool mlp_train_steps(torch::Tensor Xbf, torch::Tensor y, int64_t batch,
@@ -164,30 +289,32 @@ bool mlp_train_steps(torch::Tensor Xbf, torch::Tensor y, int64_t batch,
                      torch::Tensor m, torch::Tensor v, torch::Tensor t_dev,
                      torch::Tensor loss_out, double lr, double beta1, double beta2,
                      double eps) {
-  check(Xbf, torch::kBFloat16, "Xbf");
-  check(y, torch::kInt32, "y");
+  const int64_t N = digits_batch(Xbf, y, INT64_MAX);   // the launcher takes long long
+  // before the launcher's N % batch
+  TORCH_CHECK(batch >= 1 && batch <= INT_MAX, "batch must be 1..INT_MAX, is ", batch);
+  TORCH_CHECK(n_steps >= 0 && n_steps <= INT_MAX, "n_steps must be 0..INT_MAX, is ",
+              n_steps);
   const AdamState st = adam_state(master, bfmirror, m, v, t_dev, DIGITS_NPARAM);
-  check(loss_out, torch::kFloat32, "loss_out");
-  TORCH_CHECK(Xbf.size(1) == DIGITS_IN, "IN must be ", DIGITS_IN);
+  check_n(loss_out, torch::kFloat32, "loss_out", 1);
   const int rc = launch_mlp_train_steps(
-      bf16_ptr(Xbf), y.data_ptr<int>(), Xbf.size(0), (int)batch, (int)n_steps,
-      st.master, st.bfmirror, st.m, st.v, st.t_dev, loss_out.data_ptr<float>(),
-      (float)lr, (float)beta1, (float)beta2, (float)eps, current_stream());
-  TORCH_CHECK(rc != -2, "mlp_train_steps: hipFuncSetAttribute(LDS) failed");
-  return rc == 0;   // false -> shape constraints unmet, caller falls back
+      bf16_ptr(Xbf), y.data_ptr<int>(), N, (int)batch, (int)n_steps, st.master,
+      st.bfmirror, st.m, st.v, st.t_dev, loss_out.data_ptr<float>(), (float)lr,
+      (float)beta1, (float)beta2, (float)eps, current_stream());
+  return digits_launched(rc, "mlp_train_steps");   // false: shape constraints unmet
 }
 
 void mlp_predict(torch::Tensor X, torch::Tensor mean, torch::Tensor invstd,
                  torch::Tensor W1bf, torch::Tensor W2bf, torch::Tensor master,
                  torch::Tensor preds, c10::optional<torch::Tensor> probs) {
-  check(X, torch::kFloat32, "X");
-  check(preds, torch::kInt32, "preds");
-  TORCH_CHECK(X.size(1) == DIGITS_IN, "IN must be ", DIGITS_IN);
-  launch_mlp_predict(X.data_ptr<float>(), (int)X.size(0), mean.data_ptr<float>(),
-                     invstd.data_ptr<float>(), bf16_ptr(W1bf), bf16_ptr(W2bf),
-                     master.data_ptr<float>(), preds.data_ptr<int>(),
-                     opt_ptr<float>(probs, torch::kFloat32, "probs"),
-                     current_stream());
+  const int B = (int)check_rows(X, torch::kFloat32, "X", DIGITS_IN);
+  check_scaler(mean, invstd, DIGITS_IN);
+  digits_weights(W1bf, W2bf, master);
+  check_n(preds, torch::kInt32, "preds", B);
+  const int rc = launch_mlp_predict(
+      X.data_ptr<float>(), B, mean.data_ptr<float>(), invstd.data_ptr<float>(),
+      bf16_ptr(W1bf), bf16_ptr(W2bf), master.data_ptr<float>(),
+      preds.data_ptr<int>(), probs_ptr(probs, B, DIGITS_CLS), current_stream());
+  digits_launched(rc, "mlp_predict");
 }
 
 void adam_step(torch::Tensor master, torch::Tensor bfmirror, torch::Tensor grads,
@@ -195,16 +322,14 @@ void adam_step(torch::Tensor master, torch::Tensor bfmirror, torch::Tensor grads
                double beta1, double beta2, double eps,
                c10::optional<torch::Tensor> wimg = c10::nullopt) {
   const AdamState st = adam_state(master, bfmirror, m, v, t_dev, DIGITS_NPARAM);
-  check(grads, torch::kFloat32, "grads");
+  check_n(grads, torch::kFloat32, "grads", DIGITS_NPARAM);
   launch_adam_step(st.master, st.bfmirror, grads.data_ptr<float>(), st.m, st.v,
                    st.t_dev, (float)lr, (float)beta1, (float)beta2, (float)eps,
                    digits_wimg_ptr(wimg), current_stream());
 }
 
 torch::Tensor reduce_selftest(torch::Tensor x) {
-  check(x, torch::kFloat32, "x");
-  TORCH_CHECK(x.dim() == 2 && x.size(1) == 64, "x must be [n][64]");
-  TORCH_CHECK(x.size(0) <= INT_MAX, "too many rows");
+  check_rows(x, torch::kFloat32, "x", 64);
   torch::Tensor out = torch::empty({x.size(0), 64, 2}, x.options());
   launch_reduce_selftest(x.data_ptr<float>(), (int)x.size(0),
                          out.data_ptr<float>(), current_stream());
@@ -218,29 +343,13 @@ torch::Tensor reduce_selftest(torch::Tensor x) {
 bool mlp_step_gen(torch::Tensor Xbf, torch::Tensor y, int64_t hid, int64_t cls,
                   int64_t rt, torch::Tensor wimg, torch::Tensor master,
                   torch::Tensor slabs, double invBtot) {
-  check(Xbf, torch::kBFloat16, "Xbf");
-  check(y, torch::kInt32, "y");
-  check(wimg, torch::kBFloat16, "wimg");
-  check(master, torch::kFloat32, "master");
-  check(slabs, torch::kFloat32, "slabs");
-  const int inp = (int)Xbf.size(1);
-  const int cpad = cls <= 16 ? 16 : 32;
-  const int nparam = gen_nparam(inp, hid, cpad);
-  TORCH_CHECK(inp % 32 == 0, "staged input width must be a multiple of 32");
-  TORCH_CHECK(master.numel() >= nparam, "master too small for geometry");
-  TORCH_CHECK(wimg.numel() >= (int64_t)hid * inp + hid * 32 + cpad * hid,
-              "wimg too small for geometry");
-  TORCH_CHECK(slabs.dim() == 2 && slabs.size(1) >= nparam + 2,
-              "slabs must be [n][>= nparam+2]");
+  const GenCall a = gen_step_args(Xbf, hid, cls, "cls", rt, wimg, master, slabs);
+  check_n(y, torch::kInt32, "y", a.B, true);
   const int rc = launch_mlp_step_gen(
-      bf16_ptr(Xbf), y.data_ptr<int>(), (int)Xbf.size(0), inp, (int)hid,
-      (int)cls, (int)rt, bf16_ptr(wimg), master.data_ptr<float>(),
-      slabs.data_ptr<float>(), (int)slabs.size(1), (int)slabs.size(0),
-      (float)invBtot, current_stream());
-  TORCH_CHECK(rc != -2, "mlp_step_gen: hipFuncSetAttribute(LDS) failed");
-  TORCH_CHECK(rc != -3, "mlp_step_gen: unsupported geometry (hid=", hid,
-              " inp=", inp, " cls=", cls, " rt=", rt, ")");
-  return rc == 0;  // false -> more WGs than slab rows, caller re-sizes
+      bf16_ptr(Xbf), y.data_ptr<int>(), a.B, (int)a.g.inp, (int)hid, (int)cls,
+      (int)rt, bf16_ptr(wimg), master.data_ptr<float>(), slabs.data_ptr<float>(),
+      (int)slabs.size(1), (int)slabs.size(0), (float)invBtot, current_stream());
+  return gen_launched(rc, "mlp_step_gen", a, cls, rt);
 }
 
 void reduce_adam_gen(torch::Tensor slabs, int64_t n_wg, int64_t inp, int64_t hid,
@@ -250,39 +359,37 @@ void reduce_adam_gen(torch::Tensor slabs, int64_t n_wg, int64_t inp, int64_t hid
                      double beta1, double beta2, double eps,
                      c10::optional<torch::Tensor> wimg = c10::nullopt,
                      c10::optional<torch::Tensor> grads_out = c10::nullopt) {
-  check(counter, torch::kUInt32, "counter");
-  check(slabs, torch::kFloat32, "slabs");
-  check(loss_out, torch::kFloat32, "loss_out");
-  TORCH_CHECK(cpad == 16 || cpad == 32, "cpad must be 16 or 32");
-  const int nparam = gen_nparam(inp, hid, cpad);
-  const AdamState st = adam_state(master, bfmirror, m, v, t_dev, nparam);
-  TORCH_CHECK(slabs.dim() == 2 && slabs.size(1) >= nparam + 2, "slab stride");
-  TORCH_CHECK(n_wg >= 1 && n_wg <= slabs.size(0), "n_wg out of range");
-  launch_reduce_adam_gen(
+  const GenGeometry g = gen_geometry(inp, hid, cpad);
+  check_n(counter, torch::kUInt32, "counter", 1);
+  check_n(loss_out, torch::kFloat32, "loss_out", 1);
+  const AdamState st = adam_state(master, bfmirror, m, v, t_dev, g.nparam());
+  check_slabs(slabs, g.min_slab_stride());
+  TORCH_CHECK(n_wg >= 1 && n_wg <= slabs.size(0), "n_wg must be 1..", slabs.size(0),
+              " (the slab rows), is ", n_wg);
+  const int rc = launch_reduce_adam_gen(
       slabs.data_ptr<float>(), (int)n_wg, (int)slabs.size(1), (int)inp, (int)hid,
       (int)cpad, st.master, st.bfmirror, st.m, st.v, st.t_dev,
       loss_out.data_ptr<float>(), (float)lr, (float)beta1, (float)beta2,
-      (float)eps, opt_ptr<unsigned short>(wimg, torch::kBFloat16, "wimg"),
-      opt_ptr<float>(grads_out, torch::kFloat32, "grads_out", nparam + 1),
+      (float)eps,
+      opt_ptr<unsigned short>(wimg, torch::kBFloat16, "wimg", g.wimg_n()),
+      opt_ptr<float>(grads_out, torch::kFloat32, "grads_out", g.nparam() + 1),
       (unsigned*)counter.data_ptr(), current_stream());
+  TORCH_CHECK(rc == 0, "reduce_adam_gen: unsupported geometry");
 }
 
 void mlp_predict_gen(torch::Tensor X, int64_t inp, int64_t hid, int64_t cls,
                      torch::Tensor mean, torch::Tensor invstd, torch::Tensor wimg,
                      torch::Tensor master, torch::Tensor preds,
                      c10::optional<torch::Tensor> probs) {
-  check(X, torch::kFloat32, "X");
-  check(wimg, torch::kBFloat16, "wimg");
-  check(master, torch::kFloat32, "master");
-  check(preds, torch::kInt32, "preds");
-  TORCH_CHECK(mean.numel() == X.size(1) && invstd.numel() == X.size(1),
-              "mean/invstd must match raw feature width");
+  const GenCall a =
+      gen_predict_args(X, inp, hid, cls, "cls", mean, invstd, wimg, master);
+  check_n(preds, torch::kInt32, "preds", a.B);
   const int rc = launch_mlp_predict_gen(
-      X.data_ptr<float>(), (int)X.size(0), (int)X.size(1), (int)inp, (int)hid,
-      (int)cls, mean.data_ptr<float>(), invstd.data_ptr<float>(), bf16_ptr(wimg),
-      master.data_ptr<float>(), preds.data_ptr<int>(),
-      opt_ptr<float>(probs, torch::kFloat32, "probs"), current_stream());
-  TORCH_CHECK(rc == 0, "mlp_predict_gen: unsupported geometry or LDS failure");
+      X.data_ptr<float>(), a.B, (int)X.size(1), (int)inp, (int)hid, (int)cls,
+      mean.data_ptr<float>(), invstd.data_ptr<float>(), bf16_ptr(wimg),
+      master.data_ptr<float>(), preds.data_ptr<int>(), probs_ptr(probs, a.B, cls),
+      current_stream());
+  gen_launched(rc, "mlp_predict_gen", a, cls);
 }
 
 void adam_step_gen(torch::Tensor master, torch::Tensor bfmirror,
@@ -290,15 +397,15 @@ void adam_step_gen(torch::Tensor master, torch::Tensor bfmirror,
                    torch::Tensor t_dev, int64_t inp, int64_t hid, int64_t cpad,
                    double lr, double beta1, double beta2, double eps,
                    c10::optional<torch::Tensor> wimg = c10::nullopt) {
-  check(grads, torch::kFloat32, "grads");
-  TORCH_CHECK(cpad == 16 || cpad == 32, "cpad must be 16 or 32");
-  const int nparam = gen_nparam(inp, hid, cpad);
-  const AdamState st = adam_state(master, bfmirror, m, v, t_dev, nparam);
-  launch_adam_step_gen(st.master, st.bfmirror, grads.data_ptr<float>(), st.m,
-                       st.v, st.t_dev, nparam, (int)inp, (int)hid, (int)cpad,
-                       (float)lr, (float)beta1, (float)beta2, (float)eps,
-                       opt_ptr<unsigned short>(wimg, torch::kBFloat16, "wimg"),
-                       current_stream());
+  const GenGeometry g = gen_geometry(inp, hid, cpad);
+  check_n(grads, torch::kFloat32, "grads", g.nparam());
+  const AdamState st = adam_state(master, bfmirror, m, v, t_dev, g.nparam());
+  launch_adam_step_gen(
+      st.master, st.bfmirror, grads.data_ptr<float>(), st.m, st.v, st.t_dev,
+      (int)g.nparam(), (int)inp, (int)hid, (int)cpad, (float)lr, (float)beta1,
+      (float)beta2, (float)eps,
+      opt_ptr<unsigned short>(wimg, torch::kBFloat16, "wimg", g.wimg_n()),
+      current_stream());
 }
 
 // ---------------------------------------------------------------------------
@@ -308,37 +415,21 @@ void adam_step_gen(torch::Tensor master, torch::Tensor bfmirror,
 bool mlp_step_reg_gen(torch::Tensor Xbf, torch::Tensor Yt, int64_t hid,
                       int64_t targets, int64_t rt, torch::Tensor wimg,
                       torch::Tensor master, torch::Tensor slabs, double invBtot) {
-  check(Xbf, torch::kBFloat16, "Xbf");
-  check(Yt, torch::kFloat32, "Yt");
-  check(wimg, torch::kBFloat16, "wimg");
-  check(master, torch::kFloat32, "master");
-  check(slabs, torch::kFloat32, "slabs");
-  TORCH_CHECK(targets >= 1 && targets <= 32, "targets must be 1..32");
-  TORCH_CHECK(Xbf.dim() == 2 && Xbf.size(0) >= 1, "Xbf must be [B][inp], B >= 1");
-  const int inp = (int)Xbf.size(1);
-  const int cpad = targets <= 16 ? 16 : 32;
-  const int nparam = gen_nparam(inp, hid, cpad);
-  TORCH_CHECK(inp % 32 == 0, "staged input width must be a multiple of 32");
+  const GenCall a =
+      gen_step_args(Xbf, hid, targets, "targets", rt, wimg, master, slabs);
   // the kernel reads a row's targets as aligned 16-byte groups of a
   // [B][cpad] matrix (TabularMLPRegressor.stage_targets builds it)
-  TORCH_CHECK(Yt.dim() == 2 && Yt.size(0) == Xbf.size(0) && Yt.size(1) == cpad,
-              "Yt must be [B][", cpad, "] standardized targets, zero-padded");
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(Yt.data_ptr()) % 16 == 0,
-              "Yt must be 16-byte aligned");
-  TORCH_CHECK(master.numel() >= nparam, "master too small for geometry");
-  TORCH_CHECK(wimg.numel() >= (int64_t)hid * inp + hid * 32 + cpad * hid,
-              "wimg too small for geometry");
-  TORCH_CHECK(slabs.dim() == 2 && slabs.size(1) >= nparam + 2,
-              "slabs must be [n][>= nparam+2]");
+  check(Yt, torch::kFloat32, "Yt");
+  TORCH_CHECK(Yt.dim() == 2 && Yt.size(0) == a.B && Yt.size(1) == a.g.cpad,
+              "Yt must be [", a.B, "][", a.g.cpad,
+              "] standardized targets, zero-padded");
+  check_aligned16(Yt, "Yt");
   const int rc = launch_mlp_step_reg_gen(
-      bf16_ptr(Xbf), Yt.data_ptr<float>(), (int)Xbf.size(0), inp, (int)hid,
+      bf16_ptr(Xbf), Yt.data_ptr<float>(), a.B, (int)a.g.inp, (int)hid,
       (int)targets, (int)rt, bf16_ptr(wimg), master.data_ptr<float>(),
       slabs.data_ptr<float>(), (int)slabs.size(1), (int)slabs.size(0),
       (float)invBtot, current_stream());
-  TORCH_CHECK(rc != -2, "mlp_step_reg_gen: hipFuncSetAttribute(LDS) failed");
-  TORCH_CHECK(rc != -3, "mlp_step_reg_gen: unsupported geometry (hid=", hid,
-              " inp=", inp, " targets=", targets, " rt=", rt, ")");
-  return rc == 0;  // false -> more WGs than slab rows, caller re-sizes
+  return gen_launched(rc, "mlp_step_reg_gen", a, targets, rt);
 }
 
 void mlp_predict_reg_gen(torch::Tensor X, int64_t inp, int64_t hid,
@@ -346,35 +437,21 @@ void mlp_predict_reg_gen(torch::Tensor X, int64_t inp, int64_t hid,
                          torch::Tensor invstd, torch::Tensor wimg,
                          torch::Tensor master, torch::Tensor y_mean,
                          torch::Tensor y_scale, torch::Tensor out) {
-  check(X, torch::kFloat32, "X");
-  check(mean, torch::kFloat32, "mean");
-  check(invstd, torch::kFloat32, "invstd");
-  check(wimg, torch::kBFloat16, "wimg");
-  check(master, torch::kFloat32, "master");
-  check(y_mean, torch::kFloat32, "y_mean");
-  check(y_scale, torch::kFloat32, "y_scale");
+  const GenCall a =
+      gen_predict_args(X, inp, hid, targets, "targets", mean, invstd, wimg, master);
+  check_n(y_mean, torch::kFloat32, "y_mean", targets, true);
+  check_n(y_scale, torch::kFloat32, "y_scale", targets, true);
   check(out, torch::kFloat32, "out");
-  TORCH_CHECK(targets >= 1 && targets <= 32, "targets must be 1..32");
-  const int cpad = targets <= 16 ? 16 : 32;
-  TORCH_CHECK(X.dim() == 2 && X.size(0) >= 1 && X.size(1) <= inp,
-              "X must be [B][<= inp], B >= 1");
-  TORCH_CHECK(mean.numel() == X.size(1) && invstd.numel() == X.size(1),
-              "mean/invstd must match raw feature width");
-  TORCH_CHECK(master.numel() >= gen_nparam(inp, hid, cpad),
-              "master too small for geometry");
-  TORCH_CHECK(wimg.numel() >= hid * inp + hid * 32 + cpad * hid,
-              "wimg too small for geometry");
-  TORCH_CHECK(y_mean.numel() == targets && y_scale.numel() == targets,
-              "y_mean/y_scale must hold one entry per target");
-  TORCH_CHECK(out.dim() == 2 && out.size(0) >= X.size(0) && out.size(1) >= targets,
-              "out must be [>= B][>= targets]");
+  TORCH_CHECK(out.dim() == 2 && out.size(0) >= a.B && out.size(1) >= targets &&
+                  out.size(1) <= INT_MAX,
+              "out must be [>= ", a.B, "][>= ", targets, "]");
   const int rc = launch_mlp_predict_reg_gen(
-      X.data_ptr<float>(), (int)X.size(0), (int)X.size(1), (int)inp, (int)hid,
-      (int)targets, mean.data_ptr<float>(), invstd.data_ptr<float>(),
-      bf16_ptr(wimg), master.data_ptr<float>(), y_mean.data_ptr<float>(),
+      X.data_ptr<float>(), a.B, (int)X.size(1), (int)inp, (int)hid, (int)targets,
+      mean.data_ptr<float>(), invstd.data_ptr<float>(), bf16_ptr(wimg),
+      master.data_ptr<float>(), y_mean.data_ptr<float>(),
       y_scale.data_ptr<float>(), out.data_ptr<float>(), (int)out.size(1),
       current_stream());
-  TORCH_CHECK(rc == 0, "mlp_predict_reg_gen: unsupported geometry or LDS failure");
+  gen_launched(rc, "mlp_predict_reg_gen", a, targets);
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {

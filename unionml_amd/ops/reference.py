@@ -14,9 +14,33 @@ IN, HID, CLS, CPAD = 64, 32, 10, 16
 OFF_W1, OFF_B1, OFF_W2, OFF_B2 = 0, 2048, 2080, 2592
 NPARAM = 2608
 
-# hidden widths with a compiled gen-kernel instantiation (tabular_gen.hip)
-SUPPORTED_HID = (32, 64, 128, 256)
+# Every compiled (HID, RT, CPAD, PREDICT) instantiation of the generalized
+# kernels, both heads: the copy of TABULAR_GEN_INSTANTIATIONS in
+# hip/tabular_launch.h (tests/test_tabular_gen_cpu.py holds the two equal).
+# RT is the rows per workgroup; PREDICT marks the row whose RT the predict
+# kernel is compiled at too.
+GEN_INSTANTIATIONS = (
+    (32, 128, 16, True),
+    (32, 64, 16, False),
+    (64, 128, 16, True),
+    (64, 64, 16, False),
+    (128, 64, 16, True),
+    (128, 32, 16, False),
+    (256, 32, 16, True),
+    (32, 128, 32, True),
+    (64, 128, 32, True),
+    (128, 64, 32, True),
+    (256, 32, 32, True),
+)
+# hidden widths with a compiled gen-kernel instantiation
+SUPPORTED_HID = tuple(sorted({h for h, _, _, _ in GEN_INSTANTIATIONS}))
 MAX_CLASSES = 32
+
+
+def compiled_rts(hid: int, cpad: int) -> Tuple[int, ...]:
+    """The rows-per-workgroup values the step kernel is compiled at for a
+    padded (hid, cpad), ascending."""
+    return tuple(sorted(r for h, r, c, _ in GEN_INSTANTIATIONS if (h, c) == (hid, cpad)))
 
 # heads of the generalized kernels: softmax + cross-entropy over classes, or
 # squared error over continuous targets (TabularMLPRegressor)

@@ -111,18 +111,17 @@ class TabularMLP:
         # (tabular_launch.h); the image exists only when it is loaded
         return hip_ext().WIMG_N if self.use_spec else self.g.wimg_n
 
-    #: per hidden width: (default rows/WG, small-batch rows/WG). The
-    #: small variant keeps >= ~16 workgroups in flight at modest batch
-    #: sizes — the fwd/bwd phase is bandwidth-bound and achievable
-    #: bandwidth scales with resident CUs.
-    _GEN_RTS = {32: (128, 64), 64: (128, 64), 128: (64, 32), 256: (32, 32)}
-
     def _rows_per_wg(self, batch: Optional[int] = None) -> int:
         if self.use_spec:
             return 128
-        big, small = self._GEN_RTS[self.g.hid]
-        if self.g.cpad > 16:
-            return big  # 32-class head compiles only at the default rows/WG
+        # the default rows/WG and the small-batch one: the largest and the
+        # smallest the step kernel is compiled at for this (hid, cpad)
+        # (reference.GEN_INSTANTIATIONS; one and the same where only one
+        # is). The small variant keeps >= ~16 workgroups in flight at
+        # modest batch sizes — the fwd/bwd phase is bandwidth-bound and
+        # achievable bandwidth scales with resident CUs.
+        rts = ref.compiled_rts(self.g.hid, self.g.cpad)
+        big, small = rts[-1], rts[0]
         # smaller rows/WG doubles the grid (the bandwidth-bound fwd/bwd
         # scales with resident CUs: measured -12% at B=2048, -11% at
         # B=4096 on the MNIST shape) — but every extra WG re-reads the
@@ -195,7 +194,8 @@ class TabularMLP:
                 out = torch.empty(X.shape[0], g.inp, dtype=torch.bfloat16, device=self.device)
             else:
                 out = torch.zeros(X.shape[0], g.inp, dtype=torch.bfloat16, device=self.device)
-            hip_ext().standardize_apply(X, self.mean, self.invstd, out)
+            if X.shape[0]:
+                hip_ext().standardize_apply(X, self.mean, self.invstd, out)
             return out
         out_raw = ref.standardize_apply(X, self.mean, self.invstd)
         if g.inp == g.in_features:
@@ -438,7 +438,9 @@ class TabularMLP:
                 if return_probs
                 else None
             )
-            if self.use_spec:
+            if not X.shape[0]:   # the bindings take B >= 1: nothing to launch
+                pass
+            elif self.use_spec:
                 hip_ext().mlp_predict(
                     X, self.mean, self.invstd, self.W1bf, self.W2bf, self.master,
                     preds, probs,
