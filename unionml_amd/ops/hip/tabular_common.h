@@ -115,6 +115,77 @@ __device__ __forceinline__ float group_max(float x) {
 }
 
 // ---------------------------------------------------------------------------
+// Transposed LDS read of an MFMA 16x16x32 operand whose K axis runs DOWN the
+// rows of a row-major image T[k][stride] of 16-bit elements (gfx950
+// ds_read_b64_tr_b16).
+//
+// Operand map: lane l (lg = l>>4, lr = l&15) receives, for k-step ks, the
+// eight elements T[ks*32 + lg*8 + 0..7][tile*16 + lr] in registers 0..7. These
+// are the elements, in the register positions, that ONE ds_read_b128 of
+// TT[tile*16 + lr][ks*32 + lg*8] takes from a transposed copy TT of T, so an
+// MFMA fed either way accumulates the same products in the same order.
+//
+// The instruction, per group of 16 consecutive lanes: the group reads a block
+// of 4 rows x 16 columns; lane 4q+p of the group SUPPLIES the address of the
+// block's row q, columns 4p..4p+3 (8 bytes); lane i of the group RECEIVES
+// column i, row q in its element q. One operand is two such reads, K rows
+// +0..3 (half 0, registers 0..3) and +4..7 (half 1, registers 4..7).
+// tr_read_elem is the address a lane supplies, as an element offset from
+// T[0][0]; tr_read_map_ok replays the instruction's gather over all 64 lanes
+// and checks what each register receives against the operand map, and that
+// every address is 8-byte aligned (T[0][0] 8-byte aligned at least). A wrong
+// map is a failed static_assert, not a wrong gradient.
+//
+// EXEC: the ISA requires EXEC to be all ones for this instruction, because
+// the gather crosses lanes: a masked lane still supplies an address (whatever
+// its register holds) for data that active lanes receive. Call tr_read_k8
+// only where control flow is uniform over the wave (straight-line code, or a
+// branch on a per-wave value such as `wave < 2`, taken by all 64 lanes or by
+// none), never under a lane-dependent branch or after an early return of
+// part of the wave.
+// ---------------------------------------------------------------------------
+
+constexpr int tr_read_elem(int lane, int ks, int tile, int half, int stride) {
+  const int lg = lane >> 4, lr = lane & 15;
+  return (ks * 32 + lg * 8 + half * 4 + (lr >> 2)) * stride + tile * 16 + (lr & 3) * 4;
+}
+
+// KS k-steps of 32 rows, TILES column tiles of 16, rows of `stride` elements
+constexpr bool tr_read_map_ok(int stride, int KS, int TILES) {
+  if (stride < TILES * 16) return false;   // a row holds its columns
+  for (int ks = 0; ks < KS; ++ks)
+    for (int tile = 0; tile < TILES; ++tile)
+      for (int half = 0; half < 2; ++half)
+        for (int lane = 0; lane < 64; ++lane) {
+          if ((tr_read_elem(lane, ks, tile, half, stride) * 2) % 8 != 0) return false;
+          const int group = lane & ~15, i = lane & 15;
+          for (int q = 0; q < 4; ++q) {
+            // register half*4 + q of this lane: element i&3 of the 8 bytes
+            // that lane 4q + (i>>2) of the group points at
+            const int got = tr_read_elem(group + 4 * q + (i >> 2), ks, tile, half, stride) + (i & 3);
+            const int want_row = ks * 32 + (lane >> 4) * 8 + half * 4 + q;
+            const int want_col = tile * 16 + i;
+            if (got / stride != want_row || got % stride != want_col) return false;
+          }
+        }
+  return true;
+}
+
+template <int STRIDE, int KS, int TILES>
+__device__ __forceinline__ bf16x8 tr_read_k8(const u16 (*T)[STRIDE], int ks, int tile,
+                                             int lane) {
+  static_assert(tr_read_map_ok(STRIDE, KS, TILES), "transposed-read address map");
+  typedef __attribute__((ext_vector_type(4))) short s16x4;
+  typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+  const u16* base = &T[0][0];
+  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+      (lds_s16x4*)(base + tr_read_elem(lane, ks, tile, 0, STRIDE)));
+  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+      (lds_s16x4*)(base + tr_read_elem(lane, ks, tile, 1, STRIDE)));
+  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+
+// ---------------------------------------------------------------------------
 // Accesses to memory that another workgroup of the SAME launch writes or
 // reads (the fused step's gradient slabs and their epoch tags). Every one is
 // a global-address-space access carrying sc1: an sc1 store is written

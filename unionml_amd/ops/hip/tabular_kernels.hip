@@ -24,18 +24,22 @@
 //
 // Fragment-oriented design (2nd iteration, after PMC analysis — the first
 // scalar-read version spent 59 % of wave cycles parked on LDS latency):
-// every MFMA operand fragment is ONE ds_read_b128. An MFMA B-fragment needs
-// its K axis contiguous, so each GEMM is oriented (plain or transposed
-// output) such that both operands have a row-major LDS image whose rows run
-// along K; the small intermediates (H, dLogits) are written in BOTH
-// orientations (dual scalar stores are far cheaper than strided scalar
-// loads + register packing on the consume side).
+// every MFMA operand fragment is ONE ds_read_b128 or, where the K axis runs
+// down the image's rows, TWO ds_read_b64_tr_b16. An MFMA fragment needs
+// its K axis contiguous in the lane's registers, so the forward GEMMs and dH
+// are oriented (plain or transposed output) such that both operands have a
+// row-major LDS image whose rows run along K. The weight-grad GEMMs sum over
+// the batch row, the ROW axis of the very same images (X, H, dLogits, dH):
+// they read them with the transposed read (tr_read_k8 below), which hands
+// a lane eight K-consecutive elements of one column. Every tile has ONE
+// image. (Until r08 each of the four had a second, transposed copy written
+// with 2-byte scatter stores: profiles/r08_lds_transposed_reads.md.)
 //
 //   H^T  = W1T @ B(Xs)        A=W1T[h][k_in]   B-img = Xs[row][in]
 //   L^T  = W2T @ B(Hs)        A=W2T[c][k_h]    B-img = Hs[row][h]
 //   dH^T = W2s @ B(DLs)       A=W2s[h][k_c]    B-img = DLs[row][c]
-//   dW1^T= DHT @ B(XT)        A=DHT[h][k_row]  B-img = XT[in][row]
-//   dW2  = HT  @ B(DLT)       A=HT[h][k_row]   B-img = DLT[c][row]
+//   dW1^T= DH^T @ B(X^T)      A=tr(DHs[k_row][h])  B=tr(Xs[k_row][in])
+//   dW2  = H^T  @ B(DL^T)     A=tr(Hs[k_row][h])   B=tr(DLs[k_row][c])
 //
 // MFMA: __builtin_amdgcn_mfma_f32_16x16x32_bf16 (gfx950 2xK form), fp32
 // accumulate. Fragment mapping (verified on hardware by
@@ -45,7 +49,9 @@
 //   C/D[16x16]: lane l, reg r holds D[(l>>4)*4 + r][l&15]
 //
 // LDS row strides are multiples of 16 B (b128 alignment, guide §6 G17) with
-// bank-slot-distinct row offsets (guide §6 G4). No fp32 division in device
+// bank-slot-distinct row offsets (guide §6 G4); DHs, stored 8 bytes at a time
+// and read only transposed, has 72-byte rows (conflict-free stores; computed
+// bank figures: docs/kernels.md "LDS layout"). No fp32 division in device
 // code (v_div_scale sequences dominated the first version) — v_rcp instead.
 // All launches are stream-ordered and hipGraph-capturable (guide G9); step
 // counters live in device memory so Adam bias correction is exact under
@@ -65,7 +71,7 @@ constexpr int CPAD = DIGITS_CPAD;   // CLS padded to one MFMA tile
 // LDS strides in bf16 elements (row-major [rows][stride]):
 constexpr int XS = DIGITS_XS;   // Xs/W1T [*][72]  (144 B rows)
 #define HS 40            // Hs/DLs [ROWS][40] (80 B rows)
-#define TS 136           // XT/HT/DLT/DHT [*][136] (272 B rows)
+#define DHS 36           // DHs [ROWS][36] (72 B rows: never read by rows)
 constexpr int WS = DIGITS_WS;   // W2s/W2T [*][40] (80 B rows; K-padded zeros)
 
 // ---------------------------------------------------------------------------
@@ -179,13 +185,10 @@ constexpr int SLAB = DIGITS_SLAB;
 
 #define ALIGN16(x) (((x) + 15) & ~15)
 #define C_XS   0
-#define C_XT   ALIGN16(C_XS  + ROWS * XS * 2)
-#define C_HS   ALIGN16(C_XT  + IN * TS * 2)
-#define C_HT   ALIGN16(C_HS  + ROWS * HS * 2)
-#define C_DLS  ALIGN16(C_HT  + HID * TS * 2)
-#define C_DLT  ALIGN16(C_DLS + ROWS * HS * 2)
-#define C_DHT  ALIGN16(C_DLT + CPAD * TS * 2)
-#define C_W1T  ALIGN16(C_DHT + HID * TS * 2)
+#define C_HS   ALIGN16(C_XS  + ROWS * XS * 2)
+#define C_DLS  ALIGN16(C_HS  + ROWS * HS * 2)
+#define C_DHS  ALIGN16(C_DLS + ROWS * HS * 2)
+#define C_W1T  ALIGN16(C_DHS + ROWS * DHS * 2)
 #define C_W2S  ALIGN16(C_W1T + HID * XS * 2)
 #define C_W2T  ALIGN16(C_W2S + HID * WS * 2)
 #define C_DB1  ALIGN16(C_W2T + CPAD * WS * 2)
@@ -206,12 +209,9 @@ constexpr int SLAB = DIGITS_SLAB;
 
 struct Lds {
   u16 (*Xs)[XS];
-  u16 (*XT)[TS];
   u16 (*Hs)[HS];
-  u16 (*HT)[TS];
   u16 (*DLs)[HS];
-  u16 (*DLT)[TS];
-  u16 (*DHT)[TS];
+  u16 (*DHs)[DHS];
   u16 (*W1T)[XS];
   u16 (*W2s)[WS];
   u16 (*W2T)[WS];
@@ -226,12 +226,9 @@ struct Lds {
 __device__ __forceinline__ Lds carve(char* smem) {
   Lds L;
   L.Xs = (u16(*)[XS])(smem + C_XS);
-  L.XT = (u16(*)[TS])(smem + C_XT);
   L.Hs = (u16(*)[HS])(smem + C_HS);
-  L.HT = (u16(*)[TS])(smem + C_HT);
   L.DLs = (u16(*)[HS])(smem + C_DLS);
-  L.DLT = (u16(*)[TS])(smem + C_DLT);
-  L.DHT = (u16(*)[TS])(smem + C_DHT);
+  L.DHs = (u16(*)[DHS])(smem + C_DHS);
   L.W1T = (u16(*)[XS])(smem + C_W1T);
   L.W2s = (u16(*)[WS])(smem + C_W2S);
   L.W2T = (u16(*)[WS])(smem + C_W2T);
@@ -384,7 +381,9 @@ __device__ __forceinline__ int chunk_label(const XChunkRegs& R) {
   return R.valid ? R.label : -1;
 }
 
-// Xs row-major + XT transposed, zero batch tail
+// Xs row-major, zero batch tail. It is the ONLY image of the chunk's X: fwd1
+// reads it by rows, dW1 by transposed reads, so it stays live until every
+// wave's dW1 is done.
 __device__ __forceinline__ void store_x_chunk(const XChunkRegs& R, const Lds& L) {
   const int tid = threadIdx.x;
   #pragma unroll
@@ -394,8 +393,6 @@ __device__ __forceinline__ void store_x_chunk(const XChunkRegs& R, const Lds& L)
     const int c = (i % (IN / 8)) * 8;
     const bf16x8 v = R.vvalid[u] ? R.v[u] : (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
     *(bf16x8*)&L.Xs[r][c] = v;
-    #pragma unroll
-    for (int j = 0; j < 8; ++j) L.XT[c + j][r] = (u16)v[j];
   }
 }
 
@@ -479,7 +476,7 @@ __device__ __forceinline__ void chunk_fwd_bwd(
 
   // ---- fwd1: H^T = W1T @ B(Xs);  D: h = mt*16+lg*4+r, row = wrow+lr --------
   // hbits keeps the lane's eight H values: dH below needs exactly these
-  // (same h, same row), so it does not read HT back
+  // (same h, same row), so it does not read Hs back
   u16 hbits[HID / 16][4];
   f32x4 hacc[HID / 16];
   #pragma unroll
@@ -494,19 +491,16 @@ __device__ __forceinline__ void chunk_fwd_bwd(
   for (int mt = 0; mt < HID / 16; ++mt) {
     #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const int h = mt * 16 + lg * 4 + r;
-      const int row = wrow + lr;
       float hv = hacc[mt][r] + b1v[mt][r];
       hv = hv > 0.f ? hv : 0.f;
       const u16 hb = f2bf(hv);
       hbits[mt][r] = hb;
-      L.HT[h][row] = hb;
     }
     store_bf16x4(&L.Hs[wrow + lr][mt * 16 + lg * 4], hbits[mt]);
   }
   // NO __syncthreads here: fwd2 reads only THIS wave's rows of Hs
   // (row = wrow+lr), written by lanes of the same wave — a wave-level
-  // LDS drain is sufficient. (dW2's cross-wave HT reads are covered by
+  // LDS drain is sufficient. (dW2's cross-wave reads of Hs are covered by
   // the barrier after dH below.)
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 
@@ -534,7 +528,6 @@ __device__ __forceinline__ void chunk_fwd_bwd(
       const float dl = valid ? (e[0][r] * rs - (c == label ? 1.f : 0.f)) * invBtot : 0.f;
       const u16 dlb = f2bf(dl);
       dlbits[r] = dlb;
-      L.DLT[c][row] = dlb;
       db2_acc[r] = dl;
       if (valid && c == label) loss_acc = -(logit[0][r] - m - logs) * invBtot;
     }
@@ -559,7 +552,7 @@ __device__ __forceinline__ void chunk_fwd_bwd(
     }
   }
   // NO __syncthreads here either: dH reads only this wave's rows of
-  // DLs and HT. Cross-wave consumers (dW1/dW2 over DLT/HT) wait at the
+  // DLs. Cross-wave consumers (dW2 over all rows of Hs and DLs) wait at the
   // barrier after dH.
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 
@@ -572,15 +565,16 @@ __device__ __forceinline__ void chunk_fwd_bwd(
       const bf16x8 a = *(const bf16x8*)&L.W2s[mt * 16 + lr][lg * 8];
       const bf16x8 b = *(const bf16x8*)&L.DLs[wrow + lr][lg * 8];
       acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc, 0, 0, 0);
+      u16 dhbits[4];
       #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int h = mt * 16 + lg * 4 + r;
-        const int row = wrow + lr;
-        const float hv = bf2f(hbits[mt][r]);   // == L.HT[h][row], this lane's own store
+        const float hv = bf2f(hbits[mt][r]);   // == L.Hs[row][h], this lane's own store
         const float dh = hv > 0.f ? acc[r] : 0.f;
-        L.DHT[h][row] = f2bf(dh);
+        dhbits[r] = f2bf(dh);
         db1_acc[mt][r] = dh;
       }
+      // row-major, the lane's four consecutive h of its row as one store
+      store_bf16x4(&L.DHs[wrow + lr][mt * 16 + lg * 4], dhbits);
     }
     // db1[h]: sum this row-block's contribution across the 16 lr lanes.
     // All eight reductions first, no branch between them, then the
@@ -600,7 +594,9 @@ __device__ __forceinline__ void chunk_fwd_bwd(
       }
     }
   }
-  __syncthreads();   // DHT + per-wave partials complete
+  // DHs + per-wave partials complete; and every wave's Hs and DLs rows, which
+  // dW2 reads across waves
+  __syncthreads();
 
   // ---- db1/db2/loss += partials, waves in fixed order. The last wave does
   // it: it has no dW2 tile, so this stays off the longest wave's path ----
@@ -620,30 +616,49 @@ __device__ __forceinline__ void chunk_fwd_bwd(
     }
   }
 
-  // ---- dW1^T += DHT @ B(XT): wave tile (ht = w&1, it = w>>1) ---------------
+  // ---- dW1^T += DH^T @ B(X^T): wave tile (ht = w&1, it = w>>1). K is the
+  // batch row, the row axis of DHs and Xs: transposed reads (tr_read_k8,
+  // tabular_common.h). Every lane of every wave gets here: EXEC is full. -----
   {
     const int ht = wave & 1, it = wave >> 1;
+    // all the reads, then the MFMAs: left in one loop the compiler keeps each
+    // k-step's reads behind the previous k-step's MFMA, four LDS round trips
+    // in a row
+    bf16x8 a[ROWS / 32], b[ROWS / 32];
+    #pragma unroll
+    for (int ks = 0; ks < ROWS / 32; ++ks) {
+      a[ks] = tr_read_k8<DHS, ROWS / 32, HID / 16>(L.DHs, ks, ht, l);
+      b[ks] = tr_read_k8<XS, ROWS / 32, IN / 16>(L.Xs, ks, it, l);
+    }
+    __builtin_amdgcn_sched_barrier(0);
     f32x4 acc = acc_io.dW1;
     #pragma unroll
     for (int ks = 0; ks < ROWS / 32; ++ks) {
-      const bf16x8 a = *(const bf16x8*)&L.DHT[ht * 16 + lr][ks * 32 + lg * 8];
-      const bf16x8 b = *(const bf16x8*)&L.XT[it * 16 + lr][ks * 32 + lg * 8];
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[ks], b[ks], acc, 0, 0, 0);
     }
     acc_io.dW1 = acc;
   }
-  // ---- dW2 += HT @ B(DLT): waves 0-1 (h-tile = wave) -----------------------
+  // ---- dW2 += H^T @ B(DL^T): waves 0-1 (h-tile = wave), transposed reads of
+  // Hs and of DLs' class columns 0..15. The branch is on the wave index: all
+  // 64 lanes take it or none does, so EXEC is full inside. -------------------
   if (wave < 2) {
+    bf16x8 a[ROWS / 32], b[ROWS / 32];
+    #pragma unroll
+    for (int ks = 0; ks < ROWS / 32; ++ks) {
+      a[ks] = tr_read_k8<HS, ROWS / 32, HID / 16>(L.Hs, ks, wave, l);
+      b[ks] = tr_read_k8<HS, ROWS / 32, CPAD / 16>(L.DLs, ks, 0, l);
+    }
+    __builtin_amdgcn_sched_barrier(0);
     f32x4 acc = acc_io.dW2;
     #pragma unroll
     for (int ks = 0; ks < ROWS / 32; ++ks) {
-      const bf16x8 a = *(const bf16x8*)&L.HT[wave * 16 + lr][ks * 32 + lg * 8];
-      const bf16x8 b = *(const bf16x8*)&L.DLT[lr][ks * 32 + lg * 8];
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[ks], b[ks], acc, 0, 0, 0);
     }
     acc_io.dW2 = acc;
   }
-  if constexpr (!SINGLE) __syncthreads();   // chunk arrays free for reuse
+  // chunk arrays free for reuse: Xs above all, which dW1 has just read and
+  // the caller's next store_x_chunk refills
+  if constexpr (!SINGLE) __syncthreads();
 }
 
 // flat grads/slab index of entry i of the PART layout (db1 | db2 | loss)
@@ -743,8 +758,8 @@ mlp_step_kernel(const u16* __restrict__ Xbf, const int* __restrict__ y, int B,
 //       FIRST barrier of its workgroup, hence before that workgroup
 //       publishes; they are written by workgroup 0 as its last act, after
 //       every workgroup has published and so has read them.
-// Barriers, four per launch: after the prologue's LDS fills; after dH (DHT
-// and the per-wave partials complete); the publish barrier of (2); and the
+// Barriers, four per launch: after the prologue's LDS fills; after dH (DHs,
+// Hs, DLs and the per-wave partials complete); the publish barrier of (2); and the
 // one the polling wave joins once its poll has matched. Between the second
 // and the third each wave goes from its last MFMA straight to its slab
 // stores (chunk_fwd_bwd<true> ends in no barrier; the summing wave stores
@@ -854,7 +869,10 @@ mlp_step_fused_kernel(// the seven arguments the prologue's vector loads need
   // single-chunk form: no barrier at its end. Each wave goes from its last
   // MFMA straight to its slab stores below; the next workgroup barrier is
   // the publish barrier, and the chunk arrays are reused only behind it
-  // (the Adam-state prefetch into Xs).
+  // (the Adam-state prefetch into Xs). Xs is read until each wave's dW1,
+  // its second-to-last or last GEMM: the publish barrier is behind every
+  // wave's dW1, so the prefetch cannot overwrite rows a slower wave still
+  // has to read.
   chunk_fwd_bwd<true>(L, L.b1s, L.b2s, chunk_label(xr), xr.valid, invBtot, acc, bias_sum);
 #endif
 
@@ -893,7 +911,8 @@ mlp_step_fused_kernel(// the seven arguments the prologue's vector loads need
   // launch, so the scheme is robust to any grid size, graph replay, and
   // engine mixing; no reset. ---------------------------------------------------
   // Adam-state prefetch scratch (loads issued during the sweep below);
-  // the chunk arrays are dead from here on — reuse Xs
+  // the chunk arrays are dead behind the publish barrier (every wave's dW1
+  // reads of Xs are done there) — reuse Xs
   float* pre = (float*)L.Xs;
   const int span_pre = (NPARAM + 1 + n_wg - 1) / n_wg;
   const int lo_pre = blockIdx.x * span_pre;
