@@ -20,10 +20,12 @@ ext = CUDAExtension(
         "unionml_amd/ops/hip/tabular_ops.cpp",
         "unionml_amd/ops/hip/tabular_kernels.hip",
         "unionml_amd/ops/hip/tabular_gen.hip",
+        "unionml_amd/ops/hip/tabular_eval.hip",
     ],
     # editing a shared header rebuilds the extension
     depends=[
         "unionml_amd/ops/hip/tabular_common.h",
+        "unionml_amd/ops/hip/tabular_gen_tiles.h",
         "unionml_amd/ops/hip/tabular_launch.h",
     ],
     extra_compile_args={

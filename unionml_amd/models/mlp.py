@@ -17,7 +17,7 @@ import torch
 
 from unionml_amd import Dataset, Model
 from unionml_amd.dataset import Dataset as _Dataset
-from unionml_amd.ops.tabular import TabularMLP
+from unionml_amd.ops.tabular import TabularMLP, split_validation
 from unionml_amd.parallel import get_world_size
 from unionml_amd.serving.graph_runner import TabularGraphRunner, graphed
 from unionml_amd.utils.staging import get_stager
@@ -60,6 +60,9 @@ def trainer(
     batch_size: int = 512,
     lr: float = 2e-3,
     use_graph: bool = True,
+    validation_fraction: float = 0.0,
+    patience: int = 0,
+    restore_best: bool = False,
 ) -> TabularMLP:
     """Stage features into HBM (pinned async H2D), fit the standardizer,
     then run the fused-kernel minibatch loop. Under DP each rank gets a
@@ -68,8 +71,17 @@ def trainer(
     stager = get_stager(clf.device)
     X = stager.to_device(features.to_numpy().astype(np.float32))
     y = stager.to_device(target.squeeze().to_numpy().astype(np.int32))
+    validation = None
+    if validation_fraction > 0:
+        # hold out a seeded share of the rows; the standardizer sees the
+        # training rows only
+        tr, va = split_validation(len(X), validation_fraction)
+        Xv, yv = X[va.to(X.device)], y[va.to(y.device)]
+        X, y = X[tr.to(X.device)], y[tr.to(y.device)]
     clf.fit_standardizer(X)
     Xbf = clf.stage(X)
+    if validation_fraction > 0:
+        validation = (clf.stage(Xv), yv)
     clf.train_epochs(
         Xbf,
         y,
@@ -78,6 +90,9 @@ def trainer(
         lr=lr,
         use_graph=use_graph,
         world_size=get_world_size(),
+        validation=validation,
+        patience=patience or None,
+        restore_best=restore_best,
     )
     return clf
 
@@ -92,8 +107,12 @@ def predictor(clf: TabularMLP, features: pd.DataFrame) -> List[int]:
 
 @model.evaluator
 def evaluator(clf: TabularMLP, features: pd.DataFrame, target: pd.DataFrame) -> float:
-    preds = predictor(clf, features)
-    return float((np.asarray(preds) == target.squeeze().to_numpy()).mean())
+    """Accuracy, computed on the device by the fused evaluation kernel:
+    the count of rows whose argmax equals the label never leaves the GPU
+    as per-row predictions."""
+    X = np.ascontiguousarray(features.to_numpy(), dtype=np.float32)
+    y = target.to_numpy().reshape(-1).astype(np.int32)
+    return float(clf.evaluate_raw(torch.from_numpy(X), torch.from_numpy(y))["accuracy"])
 
 
 @model.saver

@@ -17,7 +17,7 @@ import pandas as pd
 import torch
 
 from unionml_amd import Dataset, Model
-from unionml_amd.ops.tabular import TabularMLPRegressor
+from unionml_amd.ops.tabular import TabularMLPRegressor, split_validation
 from unionml_amd.parallel import get_world_size
 from unionml_amd.serving.graph_runner import TabularGraphRunner, graphed
 from unionml_amd.utils.staging import get_stager
@@ -70,6 +70,9 @@ def trainer(
     batch_size: int = 128,
     lr: float = 5e-3,
     use_graph: bool = True,
+    validation_fraction: float = 0.0,
+    patience: int = 0,
+    restore_best: bool = False,
 ) -> TabularMLPRegressor:
     """Stage features and targets into HBM, fit BOTH standardizers (the
     network learns standardized targets), then run the fused-kernel
@@ -78,8 +81,17 @@ def trainer(
     stager = get_stager(reg.device)
     X = stager.to_device(features.to_numpy().astype(np.float32))
     Y = stager.to_device(target.to_numpy().astype(np.float32).reshape(len(target), -1))
+    validation = None
+    if validation_fraction > 0:
+        # hold out a seeded share of the rows; both standardizers see the
+        # training rows only
+        tr, va = split_validation(len(X), validation_fraction)
+        Xv, Yv = X[va.to(X.device)], Y[va.to(Y.device)]
+        X, Y = X[tr.to(X.device)], Y[tr.to(Y.device)]
     reg.fit_standardizer(X)
     reg.fit_target_standardizer(Y)
+    if validation_fraction > 0:
+        validation = (reg.stage(Xv), reg.stage_targets(Yv))
     reg.train_epochs(
         reg.stage(X),
         reg.stage_targets(Y),
@@ -88,6 +100,9 @@ def trainer(
         lr=lr,
         use_graph=use_graph,
         world_size=get_world_size(),
+        validation=validation,
+        patience=patience or None,
+        restore_best=restore_best,
     )
     return reg
 
@@ -112,11 +127,11 @@ def predictor(reg: TabularMLPRegressor, features: pd.DataFrame) -> List[float]:
 @model.evaluator
 def evaluator(reg: TabularMLPRegressor, features: pd.DataFrame, target: pd.DataFrame) -> float:
     """Coefficient of determination R^2 (1 is exact, 0 the mean predictor)."""
-    preds = np.asarray(predictor(reg, features), dtype=np.float64)
-    y = target.to_numpy().astype(np.float64).reshape(-1)
-    ss_res = float(((y - preds) ** 2).sum())
-    ss_tot = float(((y - y.mean()) ** 2).sum())
-    return 1.0 - ss_res / ss_tot
+    X = np.ascontiguousarray(features.to_numpy(), dtype=np.float32)
+    Y = target.to_numpy().astype(np.float32).reshape(len(target), -1)
+    # the squared error is summed on the device by the fused evaluation
+    # kernel; this app has one target
+    return float(reg.evaluate_raw(torch.from_numpy(X), torch.from_numpy(Y))["r2"][0])
 
 
 @model.saver

@@ -129,6 +129,20 @@ static_assert(!GenGeometry{1LL << 23, 256, 16}.ok() && !GenGeometry{48, 32, 16}.
                   !GenGeometry{32, 32, 24}.ok() && GenGeometry{1LL << 20, 256, 32}.ok(),
               "ok() refuses what an int cannot index and unpadded widths");
 
+// ---- evaluation (tabular_eval.hip): record layout ---------------------------
+
+// A workgroup's partial row and a metrics record share one layout (fp32
+// entries). Classifier: [LOSS] mean of -log softmax(z)[y], [CORRECT] the
+// rows with argmax == y, an int32 stored as its bits. Regression: [LOSS]
+// mean of 0.5 * sum_c (z - y)^2, [FIRST_MSE + c] the mean of (z - y)^2 of
+// column c < cpad in standardized units (pad columns exactly 0). The
+// partial rows hold the same entries as unnormalised fp32 sums.
+constexpr int EVAL_REC_LOSS = 0;
+constexpr int EVAL_REC_CORRECT = 1;
+constexpr int EVAL_REC_CLS_N = 2;
+constexpr int EVAL_REC_FIRST_MSE = 1;
+constexpr int eval_rec_reg_n(int cpad) { return EVAL_REC_FIRST_MSE + cpad; }
+
 // Raise a kernel's dynamic-LDS limit to `bytes`: 0, or -2 when the runtime
 // refuses. Done once per process and kernel (the flag is per instantiation),
 // as the launchers always did; per-device setup is not attempted.
@@ -227,5 +241,27 @@ int launch_mlp_predict_reg_gen(const float* X, int B, int draw, int inp, int hid
                                const float* master, const float* y_mean,
                                const float* y_scale, float* out, int ldo,
                                hipStream_t stream);
+
+// ---- tabular_eval.hip (forward-only metrics, any geometry) -------------------
+
+// rows per workgroup of the evaluation kernel for a padded (hid, cpad): the
+// RT of the table's predict row; 0 when there is none
+int eval_rows_per_wg(int hid, int cpad);
+// Two launches: the metrics kernel (one partial row per workgroup into
+// part [part_rows][part_stride]) and the finish kernel, which writes one
+// record to hist[min(*slot, cap - 1)] (rows of hist_stride floats) and
+// advances *slot. -1: fewer partial rows than workgroups; -3 also for a
+// part or hist row narrower than the record, or cap < 1.
+int launch_mlp_eval_gen(const unsigned short* Xbf, const int* y, int B, int inp,
+                        int hid, int cls, const unsigned short* wimg,
+                        const float* master, float* part, int part_rows,
+                        int part_stride, float* hist, int hist_stride, int cap,
+                        int* slot, hipStream_t stream);
+int launch_mlp_eval_reg_gen(const unsigned short* Xbf, const float* Yt, int B,
+                            int inp, int hid, int targets,
+                            const unsigned short* wimg, const float* master,
+                            float* part, int part_rows, int part_stride,
+                            float* hist, int hist_stride, int cap, int* slot,
+                            hipStream_t stream);
 
 }  // extern "C"

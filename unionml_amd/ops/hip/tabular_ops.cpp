@@ -1,7 +1,7 @@
 // Torch bindings for the CDNA4 tabular hot-path kernels
-// (tabular_kernels.hip, tabular_gen.hip; launchers and layout constants:
-// tabular_launch.h). All launches go to the current torch stream so they
-// compose with torch.cuda.graphs capture and RCCL work.
+// (tabular_kernels.hip, tabular_gen.hip, tabular_eval.hip; launchers and
+// layout constants: tabular_launch.h). All launches go to the current torch
+// stream so they compose with torch.cuda.graphs capture and RCCL work.
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
@@ -454,7 +454,102 @@ void mlp_predict_reg_gen(torch::Tensor X, int64_t inp, int64_t hid,
   gen_launched(rc, "mlp_predict_reg_gen", a, targets);
 }
 
+// ---------------------------------------------------------------------------
+// device-side evaluation (tabular_eval.hip): forward-only metrics
+// ---------------------------------------------------------------------------
+
+namespace {
+
+// An evaluation's arguments, either head: all but the per-row targets. rec
+// is the record width of the head at this geometry.
+GenCall gen_eval_args(const torch::Tensor& Xbf, int64_t hid, int64_t n_out,
+                      const char* n_out_name, bool reg, const torch::Tensor& wimg,
+                      const torch::Tensor& master, const torch::Tensor& part,
+                      const torch::Tensor& hist, const torch::Tensor& slot) {
+  const int B = (int)check_rows(Xbf, torch::kBFloat16, "Xbf");
+  check_aligned16(Xbf, "Xbf");
+  const GenGeometry g = gen_geometry_for(Xbf.size(1), hid, n_out, n_out_name);
+  const int rt = eval_rows_per_wg((int)std::min<int64_t>(hid, INT_MAX), (int)g.cpad);
+  TORCH_CHECK(rt > 0, "unsupported geometry: no evaluation kernel for hid=", hid,
+              " cpad=", g.cpad);
+  gen_weights(g, wimg, master);
+  const int64_t rec = reg ? eval_rec_reg_n((int)g.cpad) : EVAL_REC_CLS_N;
+  const int64_t n_wg = ((int64_t)B + rt - 1) / rt;
+  check(part, torch::kFloat32, "part");
+  TORCH_CHECK(part.dim() == 2 && part.size(0) >= n_wg && part.size(0) <= INT_MAX &&
+                  part.size(1) >= rec && part.size(1) <= INT_MAX,
+              "part must be [>= ", n_wg, "][>= ", rec, "], is ", part.sizes());
+  check(hist, torch::kFloat32, "hist");
+  TORCH_CHECK(hist.dim() == 2 && hist.size(0) >= 1 && hist.size(0) <= INT_MAX &&
+                  hist.size(1) >= rec && hist.size(1) <= INT_MAX,
+              "hist must be [cap >= 1][>= ", rec, "], is ", hist.sizes());
+  check_n(slot, torch::kInt32, "slot", 1);
+  return {g, B};
+}
+
+}  // namespace
+
+void mlp_eval_gen(torch::Tensor Xbf, torch::Tensor y, int64_t hid, int64_t cls,
+                  torch::Tensor wimg, torch::Tensor master, torch::Tensor part,
+                  torch::Tensor hist, torch::Tensor slot) {
+  const GenCall a =
+      gen_eval_args(Xbf, hid, cls, "cls", false, wimg, master, part, hist, slot);
+  check_n(y, torch::kInt32, "y", a.B, true);
+  const int rc = launch_mlp_eval_gen(
+      bf16_ptr(Xbf), y.data_ptr<int>(), a.B, (int)a.g.inp, (int)hid, (int)cls,
+      bf16_ptr(wimg), master.data_ptr<float>(), part.data_ptr<float>(),
+      (int)part.size(0), (int)part.size(1), hist.data_ptr<float>(),
+      (int)hist.size(1), (int)hist.size(0), slot.data_ptr<int>(), current_stream());
+  TORCH_CHECK(rc != -1, "mlp_eval_gen: fewer partial rows than workgroups");
+  gen_launched(rc, "mlp_eval_gen", a, cls);
+}
+
+void mlp_eval_reg_gen(torch::Tensor Xbf, torch::Tensor Yt, int64_t hid,
+                      int64_t targets, torch::Tensor wimg, torch::Tensor master,
+                      torch::Tensor part, torch::Tensor hist, torch::Tensor slot) {
+  const GenCall a = gen_eval_args(Xbf, hid, targets, "targets", true, wimg, master,
+                                  part, hist, slot);
+  check(Yt, torch::kFloat32, "Yt");
+  TORCH_CHECK(Yt.dim() == 2 && Yt.size(0) == a.B && Yt.size(1) == a.g.cpad,
+              "Yt must be [", a.B, "][", a.g.cpad,
+              "] standardized targets, zero-padded");
+  check_aligned16(Yt, "Yt");
+  const int rc = launch_mlp_eval_reg_gen(
+      bf16_ptr(Xbf), Yt.data_ptr<float>(), a.B, (int)a.g.inp, (int)hid,
+      (int)targets, bf16_ptr(wimg), master.data_ptr<float>(),
+      part.data_ptr<float>(), (int)part.size(0), (int)part.size(1),
+      hist.data_ptr<float>(), (int)hist.size(1), (int)hist.size(0),
+      slot.data_ptr<int>(), current_stream());
+  TORCH_CHECK(rc != -1, "mlp_eval_reg_gen: fewer partial rows than workgroups");
+  gen_launched(rc, "mlp_eval_reg_gen", a, targets);
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  // evaluation record layout (tabular_launch.h EVAL_REC_*), fp32 entries
+  m.attr("EVAL_REC_LOSS") = EVAL_REC_LOSS;
+  m.attr("EVAL_REC_CORRECT") = EVAL_REC_CORRECT;      // int32 bits
+  m.attr("EVAL_REC_CLS_N") = EVAL_REC_CLS_N;          // classifier record width
+  m.attr("EVAL_REC_FIRST_MSE") = EVAL_REC_FIRST_MSE;  // regression: + column
+  m.def("eval_rec_reg_n", [](int64_t cpad) { return eval_rec_reg_n((int)cpad); },
+        "regression record width at a padded target count", py::arg("cpad"));
+  m.def("eval_rows_per_wg",
+        [](int64_t hid, int64_t cpad) { return eval_rows_per_wg((int)hid, (int)cpad); },
+        "rows per workgroup of the evaluation kernel (0: none compiled)",
+        py::arg("hid"), py::arg("cpad"));
+  m.def("mlp_eval_gen", &mlp_eval_gen,
+        "forward-only classifier metrics: loss sum and correct count per "
+        "workgroup into part, then one record (mean loss, correct count) "
+        "into hist[min(slot, cap-1)]; slot advances",
+        py::arg("Xbf"), py::arg("y"), py::arg("hid"), py::arg("cls"),
+        py::arg("wimg"), py::arg("master"), py::arg("part"), py::arg("hist"),
+        py::arg("slot"));
+  m.def("mlp_eval_reg_gen", &mlp_eval_reg_gen,
+        "forward-only regression metrics: loss and per-column squared error "
+        "per workgroup into part, then one record (mean loss, column MSE in "
+        "standardized units) into hist[min(slot, cap-1)]; slot advances",
+        py::arg("Xbf"), py::arg("Yt"), py::arg("hid"), py::arg("targets"),
+        py::arg("wimg"), py::arg("master"), py::arg("part"), py::arg("hist"),
+        py::arg("slot"));
   // specialized (digits) layout numbers the host side stages buffers with
   m.attr("WIMG_N") = DIGITS_WIMG_N;   // packed weight image, bf16 elements
   m.attr("SLAB") = DIGITS_SLAB;       // gradient slab stride, floats

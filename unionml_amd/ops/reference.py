@@ -372,6 +372,86 @@ def mlp_predict_reg_g(
     return z[:, :T] * y_scale + y_mean
 
 
+# Evaluation record layout (fp32 entries): the copy of EVAL_REC_* in
+# hip/tabular_launch.h (tests/test_eval_cpu.py holds the two equal).
+# Classifier: [LOSS] mean loss, [CORRECT] the correct count, an int32 stored
+# as its bits. Regression: [LOSS], then the mean squared error of column c
+# at [FIRST_MSE + c], standardized units, pad columns 0.
+EVAL_REC_LOSS = 0
+EVAL_REC_CORRECT = 1
+EVAL_REC_CLS_N = 2
+EVAL_REC_FIRST_MSE = 1
+
+
+def eval_rec_n(g: Geometry) -> int:
+    """Entries of an evaluation record for the geometry's head"""
+    return EVAL_REC_FIRST_MSE + g.cpad if g.head == HEAD_REGRESSION else EVAL_REC_CLS_N
+
+
+def eval_rows_per_wg(g: Geometry) -> int:
+    """Rows per workgroup of the evaluation kernel: the RT of the table's
+    predict row for the padded (hid, cpad)."""
+    return next(r for h, r, c, p in GEN_INSTANTIATIONS if p and (h, c) == (g.hid, g.cpad))
+
+
+def _eval_logits_g(g: Geometry, Xbf, W1bf, W2bf, master) -> torch.Tensor:
+    """fp32 [B][cpad] outputs of the kernels' forward: H rounded to bf16
+    before layer 2"""
+    _, b1, _, b2 = unpack_master_g(g, master)
+    H = torch.relu(Xbf.float() @ W1bf.float() + b1)
+    return H.bfloat16().float() @ W2bf.float() + b2
+
+
+def mlp_eval_g(
+    g: Geometry,
+    Xbf: torch.Tensor,  # [B][inp] staged bf16 (zero-padded)
+    y: torch.Tensor,    # [B] int labels
+    W1bf: torch.Tensor,
+    W2bf: torch.Tensor,
+    master: torch.Tensor,
+) -> torch.Tensor:
+    """Forward-only classifier metrics, mirroring mlp_eval_gen_kernel and
+    eval_finish_kernel: one fp32 record [EVAL_REC_CLS_N] holding the mean
+    of -log softmax(z)[y] over the B rows and the count of rows with
+    argmax == y (int32 bits). A label outside [0, classes) contributes
+    exact zeros to both. Row sums are taken in fp64 and rounded once."""
+    B = Xbf.shape[0]
+    logits = _eval_logits_g(g, Xbf, W1bf, W2bf, master)[:, : g.classes]
+    yl = y.long()
+    scored = (yl >= 0) & (yl < g.classes)
+    safe = torch.where(scored, yl, torch.zeros_like(yl))
+    logp = logits - torch.logsumexp(logits, dim=1, keepdim=True)
+    row_loss = torch.where(scored, -logp.gather(1, safe[:, None])[:, 0],
+                           torch.zeros(B))
+    correct = int(((logits.argmax(dim=1) == yl) & scored).sum())
+    rec = torch.zeros(EVAL_REC_CLS_N, dtype=torch.float32)
+    rec[EVAL_REC_LOSS] = float(row_loss.double().sum() / B)
+    rec.view(torch.int32)[EVAL_REC_CORRECT] = correct
+    return rec
+
+
+def mlp_eval_reg_g(
+    g: Geometry,
+    Xbf: torch.Tensor,  # [B][inp] staged bf16 (zero-padded)
+    Yt: torch.Tensor,   # [B][cpad] fp32 standardized targets
+    W1bf: torch.Tensor,
+    W2bf: torch.Tensor,
+    master: torch.Tensor,
+) -> torch.Tensor:
+    """Forward-only regression metrics: one fp32 record
+    [EVAL_REC_FIRST_MSE + cpad] holding the mean of 0.5 * sum_{c<T} (z-y)^2
+    and each column's mean squared error in standardized units. Only the
+    real targets are read: a pad column of Yt can leak nothing."""
+    B, T = Xbf.shape[0], g.classes
+    z = _eval_logits_g(g, Xbf, W1bf, W2bf, master)
+    d = z[:, :T] - Yt.float()[:, :T]
+    sq = (d * d).double()
+    rec = torch.zeros(EVAL_REC_FIRST_MSE + g.cpad, dtype=torch.float32)
+    rec[EVAL_REC_LOSS] = float(0.5 * sq.sum() / B)
+    rec[EVAL_REC_FIRST_MSE : EVAL_REC_FIRST_MSE + T] = (sq.sum(dim=0) / B).float()
+    return rec
+
+
 def adam_step_g(
     g: Geometry,
     master: torch.Tensor,

@@ -45,6 +45,19 @@ from unionml_amd.ops.reference import (
 ADAM_BETA1, ADAM_BETA2, ADAM_EPS = 0.9, 0.999, 1e-8
 
 
+def split_validation(n: int, fraction: float, seed: int = 0):
+    """(train_idx, val_idx): a seeded random split of ``n`` rows that holds
+    out ``round(n * fraction)`` of them (at least one, at most n - 1), as
+    the app trainers' ``validation_fraction`` does it. CPU int64 tensors."""
+    if not 0.0 < fraction < 1.0:
+        raise ValueError(f"validation_fraction must be in (0, 1), is {fraction}")
+    if n < 2:
+        raise ValueError("validation_fraction needs at least two rows")
+    n_val = min(max(int(round(n * fraction)), 1), n - 1)
+    perm = torch.randperm(n, generator=torch.Generator().manual_seed(seed))
+    return perm[n_val:].sort().values, perm[:n_val].sort().values
+
+
 class TabularMLP:
     """Device-resident parameter/optimizer state + fused train/predict."""
 
@@ -94,6 +107,17 @@ class TabularMLP:
         self.counter = None     # G16 epoch counter (shared by both step modes)
         self._graph = None
         self._graph_key = None
+        # evaluation: per-workgroup partial rows, the single-record history
+        # evaluate() reads, and (digits shape only) the generalized-layout
+        # weight image the evaluation kernel reads; built on first use
+        self._eval_part = None
+        self._eval_one = None
+        self._eval_wimg = None
+        self._val_buf = None
+        #: one evaluation record per epoch of the last
+        #: train_epochs(validation=...), a CPU tensor [epochs run][record]
+        self.val_history = None
+        self._val_n = 0
         # packed weight images (kernel-layout staging) so the training
         # prologue is a straight vectorized copy; kept in sync by the
         # Adam kernels (wimg=) and rebuilt on any host-side weight
@@ -303,15 +327,20 @@ class TabularMLP:
         last loss into ``loss_out``."""
         self._launch_step(Xbf, y, invBtot, lr, loss_out)
 
-    def _run_epochs(self, run_epoch, epochs: int, key, use_graph: bool) -> float:
+    def _run_epochs(self, run_epoch, epochs: int, key, use_graph: bool,
+                    after_epoch=None) -> float:
         """Device epoch driver: one eager warmup epoch (also warms the
         RCCL communicator / memory pool), then capture one epoch into a
         hipGraph once per ``key`` (capture records without executing)
         and replay the remaining epochs — or step them eagerly when
         ``use_graph`` is off or capture fails. Returns the last loss,
-        which both step flavours leave in grads[nparam]."""
+        which both step flavours leave in grads[nparam]. ``after_epoch(e)``
+        (validation with patience or restore_best only) runs on the host
+        after epoch ``e`` and returns True to stop."""
         run_epoch()
         remaining = epochs - 1
+        if after_epoch is not None and after_epoch(0):
+            remaining = 0
         if use_graph and self._graph_key != key:
             try:
                 gph = torch.cuda.CUDAGraph()
@@ -321,16 +350,16 @@ class TabularMLP:
             except RuntimeError as exc:  # e.g. RCCL capture unsupported
                 logger.warning("hipGraph capture failed (%s); eager stepping", exc)
                 self._graph, self._graph_key = None, None
-        if use_graph and self._graph is not None:
-            for _ in range(remaining):
-                self._graph.replay()
-        else:
-            for _ in range(remaining):
-                run_epoch()
+        replay = self._graph.replay if use_graph and self._graph is not None else run_epoch
+        for e in range(remaining):
+            replay()
+            if after_epoch is not None and after_epoch(e + 1):
+                break
         torch.cuda.synchronize(self.device)
         return float(self.grads[self.g.nparam].item())
 
-    def _train_epochs_fused(self, Xbf, y, batches, *, epochs, lr, use_graph) -> float:
+    def _train_epochs_fused(self, Xbf, y, batches, *, epochs, lr, use_graph,
+                            val=None) -> float:
         g = self.g
         self._ensure_slabs(
             max(
@@ -345,11 +374,21 @@ class TabularMLP:
                 self._fused_adam_step(
                     Xbf[off : off + bs], y[off : off + bs], 1.0 / bs, lr, loss_out
                 )
+            if val is not None:
+                # same stream, after the epoch's last step: still one chain
+                self._eval_launch(val.X, val.y, val.hist, val.slot)
 
         # the capture bakes in every batch's offset, row count and 1/bs:
         # the key is the batch list itself, not its length
         key = ("fused", tuple(batches), lr, Xbf.data_ptr(), y.data_ptr())
-        return self._run_epochs(run_epoch, epochs, key, use_graph)
+        if val is None:
+            return self._run_epochs(run_epoch, epochs, key, use_graph)
+        # ... and the validation rows, the history (its row count is the
+        # finish kernel's cap) and the slot
+        key += ("val", val.X.data_ptr(), val.y.data_ptr(), val.X.shape[0],
+                val.hist.data_ptr(), val.hist.shape[0], val.slot.data_ptr())
+        return self._run_epochs(run_epoch, epochs, key, use_graph,
+                                after_epoch=val.after_epoch if val.on_host else None)
 
     def train_epochs(
         self,
@@ -362,14 +401,43 @@ class TabularMLP:
         use_graph: bool = True,
         world_size: int = 1,
         engine: str = "auto",
+        validation=None,
+        patience: Optional[int] = None,
+        min_delta: float = 0.0,
+        restore_best: bool = False,
     ) -> float:
         """Minibatch Adam training over the staged (bf16) features.
 
         Returns the last step's loss. ``world_size > 1`` means this rank
         holds a shard and gradients all-reduce over RCCL each step.
+
+        ``validation=(Xv, yv)`` (staged like ``Xbf`` and ``y``) ends every
+        epoch in a device-side evaluation of those rows, inside the
+        captured epoch when ``use_graph`` is on; ``val_history`` then
+        holds one record per epoch. ``patience`` stops when the validation
+        loss has not improved by more than ``min_delta`` for that many
+        epochs, ``restore_best`` puts back the weights and optimizer state
+        of the best epoch; either costs one host sync per epoch.
         """
         g = self.g
         y = self._prep_targets(y)
+        val = None
+        if validation is None:
+            if patience is not None or restore_best:
+                raise ValueError("patience and restore_best need validation=(Xv, yv)")
+        else:
+            if world_size > 1:
+                raise ValueError(
+                    "validation is not supported under data parallel (world_size > 1)"
+                )
+            if engine == "persistent":
+                raise ValueError(
+                    "validation is not supported by engine='persistent': the "
+                    "persistent kernel runs all epochs in one launch"
+                )
+            if patience is not None and patience < 1:
+                raise ValueError(f"patience must be >= 1, is {patience}")
+            val = _Validation(self, validation, epochs, patience, min_delta, restore_best)
         n = Xbf.shape[0]
         batches = [
             (off, min(batch_size, n - off)) for off in range(0, n, batch_size)
@@ -400,9 +468,15 @@ class TabularMLP:
                     # fused/adam step (wimg=) doesn't load stale weights
                     self._build_wimg()
                     return float(loss_out.item())
-            return self._train_epochs_fused(
-                Xbf, y, batches, epochs=epochs, lr=lr, use_graph=use_graph
+            if val is None:
+                return self._train_epochs_fused(
+                    Xbf, y, batches, epochs=epochs, lr=lr, use_graph=use_graph
+                )
+            loss = self._train_epochs_fused(
+                Xbf, y, batches, epochs=epochs, lr=lr, use_graph=use_graph, val=val
             )
+            val.finish()
+            return loss
 
         def run_epoch():
             last = None
@@ -418,13 +492,132 @@ class TabularMLP:
 
         if not (self.use_hip and use_graph):
             loss = None
-            for _ in range(epochs):
+            for e in range(epochs):
                 loss = run_epoch()
+                if val is not None and val.after_epoch_ref(e):
+                    break
+            if val is not None:
+                val.finish()
             # with allreduce the stored loss is already the global mean
             return float(loss.item()) if loss is not None else float("nan")
 
         key = (n, batch_size, world_size, lr, Xbf.data_ptr(), y.data_ptr())
         return self._run_epochs(run_epoch, epochs, key, use_graph=True)
+
+    # -- evaluation ------------------------------------------------------------
+
+    def _rec_layout(self):
+        """Where the evaluation record's entries are: the extension's
+        constants on the GPU, reference.py's copy on the CPU."""
+        return hip_ext() if self.use_hip else ref
+
+    def _eval_rec_n(self) -> int:
+        return self._rec_layout().EVAL_REC_CLS_N
+
+    def _ensure_eval(self, n_rows: int):
+        """Device buffers of an evaluation over ``n_rows`` rows."""
+        g = self.g
+        rt = hip_ext().eval_rows_per_wg(g.hid, g.cpad)
+        n_wg = (n_rows + rt - 1) // rt
+        if self._eval_part is None or self._eval_part.shape[0] < n_wg:
+            self._eval_part = torch.zeros(
+                n_wg, self._eval_rec_n(), dtype=torch.float32, device=self.device
+            )
+            # a captured epoch holds the old buffer's address
+            self._graph = self._graph_key = None
+        if self._eval_one is None:
+            self._eval_one = (
+                torch.zeros(1, self._eval_rec_n(), dtype=torch.float32, device=self.device),
+                torch.zeros(1, dtype=torch.int32, device=self.device),
+            )
+        if self.use_spec and self._eval_wimg is None:
+            self._eval_wimg = torch.zeros(g.wimg_n, dtype=torch.bfloat16, device=self.device)
+            self._graph = self._graph_key = None
+
+    def _refresh_eval_wimg(self):
+        """Digits shape: the specialized kernels keep their own image
+        layout, the evaluation kernel is the generalized <32,128,16> one.
+        Rebuild its image (the packing of _build_wimg's generalized branch)
+        from bfmirror with device ops, capturable, before each evaluation."""
+        g = self.g
+        img = self._eval_wimg
+        o1 = g.hid * g.inp
+        o2 = o1 + g.hid * 32
+        img[:o1].view(g.hid, g.inp).copy_(self.W1bf.t())               # W1T[h][k]
+        img[o1:o2].view(g.hid, 32)[:, : g.cpad].copy_(self.W2bf)       # W2s K-pad
+        img[o2:].view(g.cpad, g.hid).copy_(self.W2bf.t())              # W2T[c][h]
+
+    def _eval_launch(self, Xbf, y, hist, slot):
+        """The evaluation's two launches (metrics, then finish) on the
+        current stream: one record into hist[min(slot, cap-1)], slot + 1."""
+        wimg = self.wimg
+        if self.use_spec:
+            self._refresh_eval_wimg()
+            wimg = self._eval_wimg
+        self._eval_kernel(hip_ext(), Xbf, y, wimg, hist, slot)
+
+    def _eval_kernel(self, ext, Xbf, y, wimg, hist, slot):
+        """The generalized family's evaluation kernel, by head."""
+        g = self.g
+        ext.mlp_eval_gen(
+            Xbf, y, g.hid, g.classes, wimg, self.master, self._eval_part, hist, slot
+        )
+
+    def _ref_eval(self, Xbf, y) -> torch.Tensor:
+        """The CPU path's evaluation record (torch reference), by head."""
+        return ref.mlp_eval_g(self.g, Xbf, y, self.W1bf, self.W2bf, self.master)
+
+    def _eval_record(self, Xbf, y) -> torch.Tensor:
+        """One evaluation record of the staged rows, on the CPU."""
+        if not self.use_hip:
+            return self._ref_eval(Xbf, y)
+        self._ensure_eval(Xbf.shape[0])
+        hist, slot = self._eval_one
+        slot.zero_()
+        self._eval_launch(Xbf, y, hist, slot)
+        return hist[0].cpu()
+
+    def _decode_record(self, rec: torch.Tensor, n: int) -> dict:
+        L = self._rec_layout()
+        correct = int(rec.view(torch.int32)[L.EVAL_REC_CORRECT])
+        return {"loss": float(rec[L.EVAL_REC_LOSS]), "accuracy": correct / n, "n": n}
+
+    def _empty_metrics(self) -> dict:
+        return {"loss": float("nan"), "accuracy": float("nan"), "n": 0}
+
+    def _eval_inputs(self, Xbf, y):
+        Xbf = Xbf.to(self.device).contiguous()
+        y = self._prep_targets(y)
+        if Xbf.dim() != 2 or Xbf.shape[1] != self.g.inp or Xbf.dtype != torch.bfloat16:
+            raise ValueError(
+                f"Xbf must be the staged bf16 [N][{self.g.inp}] features (stage), "
+                f"got {Xbf.dtype} {tuple(Xbf.shape)}"
+            )
+        if y.shape[0] != Xbf.shape[0]:
+            raise ValueError(f"{Xbf.shape[0]} rows but {y.shape[0]} targets")
+        return Xbf, y
+
+    def evaluate(self, Xbf: torch.Tensor, y: torch.Tensor) -> dict:
+        """Mean cross-entropy and accuracy of the staged rows (``stage``),
+        computed on the device by the fused evaluation kernel:
+        ``{"loss", "accuracy", "n"}``. A label outside ``[0, classes)``
+        counts as a row that is neither scored nor correct. An empty input
+        gives ``n = 0`` and NaN metrics."""
+        Xbf, y = self._eval_inputs(Xbf, y)
+        n = Xbf.shape[0]
+        if not n:
+            return self._empty_metrics()
+        return self._decode_record(self._eval_record(Xbf, y), n)
+
+    def evaluate_raw(self, X: torch.Tensor, y: torch.Tensor) -> dict:
+        """``evaluate`` of raw fp32 features: stages them first."""
+        return self.evaluate(self.stage(torch.as_tensor(X)), torch.as_tensor(y))
+
+    def val_metrics(self):
+        """``val_history`` as a list of dicts, one per epoch."""
+        if self.val_history is None:
+            return []
+        return [self._decode_record(r, self._val_n) for r in self.val_history]
 
     # -- inference -------------------------------------------------------------
 
@@ -465,6 +658,7 @@ class TabularMLP:
         d = dict(self.__dict__)
         d["slabs"] = d["counter"] = None
         d["_graph"] = d["_graph_key"] = None
+        d["_eval_part"] = d["_eval_one"] = d["_eval_wimg"] = d["_val_buf"] = None
         d["wimg"] = None
         d["device"] = str(self.device)
         for k, v in list(d.items()):
@@ -478,6 +672,9 @@ class TabularMLP:
             device = torch.device("cpu")
         state.setdefault("g", Geometry(64, 32, 10))       # pre-geometry pickles
         state.setdefault("use_spec", state["g"].is_specialized)
+        for k in ("_eval_part", "_eval_one", "_eval_wimg", "_val_buf", "val_history"):
+            state.setdefault(k, None)                     # pre-evaluation pickles
+        state.setdefault("_val_n", 0)
         self.__dict__.update(state)
         self.device = device
         self.use_hip = device.type == "cuda"
@@ -545,6 +742,77 @@ class TabularMLP:
             self.t_dev.zero_()
         self._graph = self._graph_key = None
         self._build_wimg()
+
+
+class _Validation:
+    """One train_epochs call's validation pass: the staged held-out rows,
+    the per-epoch record history and its device slot, and the host-side
+    early-stopping / best-snapshot bookkeeping."""
+
+    STATE = ("master", "bfmirror", "m", "v", "t_dev")
+
+    def __init__(self, model, validation, epochs, patience, min_delta, restore_best):
+        self.model = model
+        self.X, self.y = model._eval_inputs(*validation)
+        if not self.X.shape[0]:
+            raise ValueError("validation needs at least one row")
+        self.patience, self.min_delta = patience, float(min_delta)
+        self.restore_best = restore_best
+        self.on_host = patience is not None or restore_best
+        self.best, self.bad, self.snap, self.ran = float("inf"), 0, None, 0
+        self.records = []           # CPU path
+        self.hist = self.slot = None
+        if model.use_hip:
+            model._ensure_eval(self.X.shape[0])
+            buf = model._val_buf
+            if buf is None or buf[0].shape[0] != epochs:
+                # cap = epochs is baked into a captured finish launch
+                buf = model._val_buf = (
+                    torch.empty(epochs, model._eval_rec_n(), dtype=torch.float32,
+                                device=model.device),
+                    torch.empty(1, dtype=torch.int32, device=model.device),
+                )
+            self.hist, self.slot = buf
+            self.hist.zero_()
+            self.slot.zero_()       # before the first epoch
+
+    def _track(self, loss: float) -> bool:
+        """Bookkeeping after an epoch whose validation loss is ``loss``:
+        True to stop."""
+        self.ran += 1
+        if not self.on_host:
+            return False
+        if loss < self.best - self.min_delta:
+            self.best, self.bad = loss, 0
+            if self.restore_best:
+                self.snap = {k: getattr(self.model, k).clone() for k in self.STATE}
+        else:
+            self.bad += 1
+        return self.patience is not None and self.bad >= self.patience
+
+    def after_epoch(self, e: int) -> bool:
+        """Device path: read epoch ``e``'s record (one sync)."""
+        L = self.model._rec_layout()
+        return self._track(float(self.hist[e, L.EVAL_REC_LOSS].item()))
+
+    def after_epoch_ref(self, e: int) -> bool:
+        """CPU path: evaluate, record, track."""
+        rec = self.model._ref_eval(self.X, self.y)
+        self.records.append(rec)
+        return self._track(float(rec[self.model._rec_layout().EVAL_REC_LOSS]))
+
+    def finish(self):
+        m = self.model
+        if m.use_hip:
+            ran = self.ran if self.on_host else int(self.slot.item())
+            m.val_history = self.hist[:ran].cpu()
+        else:
+            m.val_history = torch.stack(self.records)
+        m._val_n = self.X.shape[0]
+        if self.restore_best and self.snap is not None:
+            for k, t in self.snap.items():
+                getattr(m, k).copy_(t)
+            m._build_wimg()
 
 
 class TabularMLPRegressor(TabularMLP):
@@ -640,6 +908,63 @@ class TabularMLPRegressor(TabularMLP):
         ref.mlp_step_reg_g(
             self.g, Xbf, Yt, self.W1bf, self.W2bf, self.master, self.grads, invBtot
         )
+
+    # -- evaluation ------------------------------------------------------------
+
+    def _eval_rec_n(self) -> int:
+        L = self._rec_layout()
+        return L.EVAL_REC_FIRST_MSE + self.g.cpad
+
+    def _eval_kernel(self, ext, Xbf, Yt, wimg, hist, slot):
+        g = self.g
+        ext.mlp_eval_reg_gen(
+            Xbf, Yt, g.hid, g.classes, wimg, self.master, self._eval_part, hist, slot
+        )
+
+    def _ref_eval(self, Xbf, Yt) -> torch.Tensor:
+        return ref.mlp_eval_reg_g(self.g, Xbf, Yt, self.W1bf, self.W2bf, self.master)
+
+    def _decode_record(self, rec: torch.Tensor, n: int, sst=None) -> dict:
+        """mse per target in original units (the column MSE times
+        y_scale^2); with ``sst`` (per-target total sum of squares in
+        standardized units) also r2 = 1 - SSE / SST."""
+        L = self._rec_layout()
+        T = self.g.classes
+        col = rec[L.EVAL_REC_FIRST_MSE : L.EVAL_REC_FIRST_MSE + T].double()
+        mse = col * self.y_scale.detach().cpu().double() ** 2
+        out = {"loss": float(rec[L.EVAL_REC_LOSS]), "mse": mse.tolist(),
+               "mse_mean": float(mse.mean()), "n": n}
+        if sst is not None:
+            r2 = 1.0 - col * n / sst
+            out["r2"] = r2.tolist()
+            out["r2_mean"] = float(r2.mean())
+        return out
+
+    def _empty_metrics(self) -> dict:
+        nan = float("nan")
+        T = self.g.classes
+        return {"loss": nan, "mse": [nan] * T, "mse_mean": nan, "r2": [nan] * T,
+                "r2_mean": nan, "n": 0}
+
+    def evaluate(self, Xbf: torch.Tensor, Yt: torch.Tensor) -> dict:
+        """Metrics of the staged rows against staged targets
+        (``stage_targets``), on the device: ``{"loss", "mse", "r2", "n"}``
+        plus ``mse_mean`` / ``r2_mean`` over the targets. ``loss`` is the
+        training loss (half the squared error summed over targets, mean
+        over rows, standardized units); ``mse`` and ``r2`` are per target,
+        ``mse`` in original target units. The total sum of squares behind
+        ``r2`` comes from ordinary torch ops on the staged targets."""
+        Xbf, Yt = self._eval_inputs(Xbf, Yt)
+        n = Xbf.shape[0]
+        if not n:
+            return self._empty_metrics()
+        Yr = Yt[:, : self.g.classes].double()
+        sst = ((Yr - Yr.mean(dim=0)) ** 2).sum(dim=0).cpu()
+        return self._decode_record(self._eval_record(Xbf, Yt), n, sst)
+
+    def evaluate_raw(self, X: torch.Tensor, Y: torch.Tensor) -> dict:
+        """``evaluate`` of raw features and raw targets: stages both."""
+        return self.evaluate(self.stage(torch.as_tensor(X)), self.stage_targets(Y))
 
     def train_epochs(self, Xbf: torch.Tensor, Yt: torch.Tensor, *,
                      engine: str = "auto", **kwargs) -> float:
