@@ -8,6 +8,15 @@
 // (the -mllvm flag is the extension's, setup.py: without it the probe times
 // a kernel that fetches its first arguments by a scalar load)
 //
+// Two more switches, for the tail behind the hand-off:
+//   -DPROBE_CONST_CORR   the Adam bias corrections are constants (no pow):
+//                        base minus this is what the two pow expansions cost
+//   -DPROBE_COUNT_POLLS  workgroup 0's polling wave bins its poll rounds per
+//                        launch (1 .. 13, 14+) in the spare words behind slab
+//                        0's tag; the probe prints the histogram of the timed
+//                        launches (the atomic add is in the timing: read the
+//                        counts of this build, not its time)
+//
 #include "../unionml_amd/ops/hip/tabular_kernels.hip"
 
 #include <cstdio>
@@ -61,6 +70,11 @@ int main(int argc, char** argv) {
     }
   }
   CHECK(hipDeviceSynchronize());
+#ifdef PROBE_COUNT_POLLS
+  constexpr int POLL_BINS = SLAB - (NPARAM + 2);
+  static_assert(POLL_BINS >= 14, "the kernel's bins fit behind slab 0's tag");
+  CHECK(hipMemset(slabs + NPARAM + 2, 0, POLL_BINS * 4));   // drop the warm-up's
+#endif
 
   hipEvent_t t0, t1;
   CHECK(hipEventCreate(&t0));
@@ -76,5 +90,12 @@ int main(int argc, char** argv) {
   float ms = 0.f;
   CHECK(hipEventElapsedTime(&ms, t0, t1));
   printf("B=%d n_wg=%d us_per_launch=%.3f\n", B, n_wg, ms * 1000.0f / iters);
+#ifdef PROBE_COUNT_POLLS
+  unsigned bins[POLL_BINS];
+  CHECK(hipMemcpy(bins, slabs + NPARAM + 2, sizeof(bins), hipMemcpyDeviceToHost));
+  printf("poll rounds per launch (1 .. 13, 14+):");
+  for (int k = 0; k < 14; ++k) printf(" %u", bins[k]);
+  printf("\n");
+#endif
   return 0;
 }

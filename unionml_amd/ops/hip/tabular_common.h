@@ -244,11 +244,16 @@ __device__ __forceinline__ float adam_corr(float beta_pow_t) {
   return fast_rcp(1.f - beta_pow_t);
 }
 
-// both factors for step t (the step being applied, counted from 1)
+// one factor for step t (the step being applied, counted from 1)
+__device__ __forceinline__ float adam_bias_corr_one(float beta, float t) {
+  return adam_corr(__powf(beta, t));
+}
+
+// both factors for step t
 __device__ __forceinline__ void adam_bias_corr(float beta1, float beta2, float t,
                                                float& corr1, float& corr2) {
-  corr1 = adam_corr(__powf(beta1, t));
-  corr2 = adam_corr(__powf(beta2, t));
+  corr1 = adam_bias_corr_one(beta1, t);
+  corr2 = adam_bias_corr_one(beta2, t);
 }
 
 // p/m/v hold the old values on entry and the new ones on return. With rn()

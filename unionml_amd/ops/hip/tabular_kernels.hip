@@ -766,6 +766,18 @@ mlp_step_kernel(const u16* __restrict__ Xbf, const int* __restrict__ y, int B,
 // db1 / db2 / loss from a register).
 // ---------------------------------------------------------------------------
 
+// The stripe threads. Wave 0 is the hand-off wave and nothing else (it stores
+// the tag, polls and joins the barrier); the stripe of the Adam-state prefetch
+// and of the reduce loop belongs to waves 1 to 7: thread tid >= STRIPE_T0
+// takes i = lo + (tid - STRIPE_T0), then every STRIPE_STEP-th. Both loops go
+// through stripe_first, so a thread reads back exactly the pre[] entries it
+// wrote. The stripe gets no longer for it: ceil(span / 448) == ceil(span / 512)
+// for the spans of 1 to 5 workgroups (2609, 1305, 870, 653, 522), and from 6
+// workgroups on it is one iteration.
+constexpr int STRIPE_T0 = 64;
+constexpr int STRIPE_STEP = BLOCK - STRIPE_T0;
+__device__ __forceinline__ int stripe_first(int lo, int tid) { return lo + (tid - STRIPE_T0); }
+
 extern "C" __global__ void __launch_bounds__(BLOCK)
 mlp_step_fused_kernel(// the seven arguments the prologue's vector loads need
                       // come first: 14 dwords, inside the 16 that the build's
@@ -804,7 +816,8 @@ mlp_step_fused_kernel(// the seven arguments the prologue's vector loads need
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const Lds L = carve(smem);
   // L.loss slots: [0] unused here (the loss travels in a register),
-  // [1] poll verdict (0 ok, 1 timed out)
+  // [1] poll verdict (0 ok, 1 timed out), [2] and [3] the Adam bias
+  // corrections on their way from waves 1 and 2 to the stripe threads
   unsigned* lossu = (unsigned*)L.loss;
 
   const int tid = threadIdx.x;
@@ -918,6 +931,8 @@ mlp_step_fused_kernel(// the seven arguments the prologue's vector loads need
   const int lo_pre = blockIdx.x * span_pre;
   const bool use_pre =
       (grads_out == nullptr) && (3 * span_pre * 4 <= ROWS * XS * 2);
+  const float t_new = (float)(t_pre + 1u);
+  float corr1 = 0.f, corr2 = 0.f;   // Adam bias corrections (fused mode only)
 #ifndef PROBE_SKIP_HANDSHAKE
   // Condition (2): EVERY storing wave waits until its write-through stores
   // have completed (inline asm, so no compiler pass can drop the wait), and
@@ -929,25 +944,60 @@ mlp_step_fused_kernel(// the seven arguments the prologue's vector loads need
   if (tid == 0) xwg_store((unsigned*)(slab + NPARAM + 1), epoch);   // (3)
   // No barrier between the tag store and the polls: nothing reads what the
   // tag store orders. Lane 0 sits in the polling wave itself, the other
-  // waves only prefetch their own Adam stripe until the barrier behind the
+  // waves only work on their own Adam stripe until the barrier behind the
   // poll, and another workgroup sees the tag whenever it arrives.
 
-  // prefetch this WG's Adam-state stripe (master/m/v) into LDS WHILE the
-  // sweep waits — these are only ever written by this same WG's stripe
-  // in the reduce phase, so plain loads ahead of the poll are safe
-  // (condition (4)), and it pulls an HBM round trip out of the reduce
-  // chain.
-  if (use_pre) {
+  // Two roles until that barrier. Wave 0 is the hand-off wave and nothing
+  // else: from the tag store it goes straight to its first poll, with no
+  // load of its own to wait for. Waves 1 to 7 do two things WHILE the sweep
+  // waits. They prefetch this WG's Adam-state stripe (master/m/v) into LDS —
+  // these are only ever written by this same WG's stripe in the reduce
+  // phase, so plain loads ahead of the poll are safe (condition (4)), and it
+  // pulls an HBM round trip out of the reduce chain. And two of them compute
+  // the Adam bias corrections, two full pow expansions whose only inputs
+  // (beta1, beta2, t_pre) every thread has held since the prologue: wave 1
+  // corr1, wave 2 corr2, one chain each, so that the pair takes the time of
+  // one (both chains in every stripe wave outlast the poll and hold the
+  // barrier up). The stripe's first loads go out, the arithmetic runs while
+  // they are in flight, and the empty asm pins it here (left alone the
+  // compiler sinks the pure arithmetic to its use, behind the last barrier
+  // and in front of the first slab load). The values cross the barrier in
+  // L.loss[2] and [3]. Reduce-only launches need no correction and compute
+  // none.
+  if (wave != 0) {
     const int hi_pre = min(lo_pre + span_pre, NPARAM);
-    for (int i = lo_pre + tid; i < hi_pre; i += BLOCK) {
-      const int j = i - lo_pre;
-      pre[j] = master[i];
-      pre[span_pre + j] = m[i];
-      pre[2 * span_pre + j] = v[i];
+    int i = stripe_first(lo_pre, tid);
+    const bool first = use_pre && i < hi_pre;
+    float p0 = 0.f, m0 = 0.f, v0 = 0.f;
+    if (first) {
+      p0 = master[i];
+      m0 = m[i];
+      v0 = v[i];
     }
-  }
-
-  if (wave == 0) {
+    if (!grads_out && wave <= 2) {
+#ifdef PROBE_CONST_CORR
+      const float c = wave == 1 ? 10.f : 1000.f;   // timing probe: no pow
+#else
+      const float c = adam_bias_corr_one(wave == 1 ? beta1 : beta2, t_new);
+#endif
+      asm volatile("" :: "v"(c));
+      if (l == 0) L.loss[1 + wave] = c;
+    }
+    if (first) {
+      const int j = i - lo_pre;
+      pre[j] = p0;
+      pre[span_pre + j] = m0;
+      pre[2 * span_pre + j] = v0;
+    }
+    if (use_pre) {
+      for (i += STRIPE_STEP; i < hi_pre; i += STRIPE_STEP) {
+        const int j = i - lo_pre;
+        pre[j] = master[i];
+        pre[span_pre + j] = m[i];
+        pre[2 * span_pre + j] = v[i];
+      }
+    }
+  } else {
     // relaxed PARALLEL sweep: lane j polls tags j, j+64, ... (G16: never
     // poll with an acquire). One vector gather per poll round — one
     // memory round trip after the last publish, independent of n_wg
@@ -965,6 +1015,18 @@ mlp_step_fused_kernel(// the seven arguments the prologue's vector loads need
       }
       if (!ok) break;
     }
+#ifdef PROBE_COUNT_POLLS
+    {
+      // counting probe: the wave's poll rounds (its slowest lane's), binned
+      // 1 .. 13 and 14+ in the spare words behind slab 0's tag
+      unsigned rounds = spins + 1u;
+      #pragma unroll
+      for (int o = 32; o > 0; o >>= 1) rounds = max(rounds, (unsigned)__shfl_xor((int)rounds, o));
+      if (l == 0 && blockIdx.x == 0) {
+        atomicAdd((unsigned*)(slabs + NPARAM + 2) + (min(rounds, 14u) - 1u), 1u);
+      }
+    }
+#endif
     const unsigned long long bad = __ballot(!ok);
     // No agent acquire: every slab load below is an sc1 load, which does
     // not look into this CU's L1, so there is no stale line to invalidate
@@ -990,13 +1052,16 @@ mlp_step_fused_kernel(// the seven arguments the prologue's vector loads need
   return;
 #endif
   // ---- every WG reduces its own param stripe + applies Adam ----------------
-  const float t_new = (float)(t_pre + 1u);
-  float corr1, corr2;
-  adam_bias_corr(beta1, beta2, t_new, corr1, corr2);
+#ifdef PROBE_SKIP_HANDSHAKE
+  // timing probe without the hand-off window: the corrections at their use
+  if (!grads_out) adam_bias_corr(beta1, beta2, t_new, corr1, corr2);
+#else
+  if (!grads_out) corr1 = L.loss[2], corr2 = L.loss[3];
+#endif
   const int span = (NPARAM + 1 + n_wg - 1) / n_wg;
   const int lo = blockIdx.x * span;
   const int hi = min(lo + span, NPARAM + 1);
-  for (int i = lo + tid; i < hi; i += BLOCK) {
+  for (int i = stripe_first(lo, tid); wave != 0 && i < hi; i += STRIPE_STEP) {
     // Eight chains: chain k sums the slabs w = k, k+8, k+16, ... in that
     // order; the remainder (n_wg % 8 slabs) goes into chain 0; then the
     // chains are folded pairwise. That order is pinned bit for bit. What is
@@ -1075,35 +1140,44 @@ adam_step_kernel(float* __restrict__ master, u16* __restrict__ bfmirror,
                  float lr, float beta1, float beta2, float eps,
                  u16* __restrict__ wimg) {
   __shared__ float corr1, corr2;
+  // 4 strided elements per thread and iteration, all their loads issued
+  // before the first use, so the g/m/v/master reads overlap instead of
+  // serializing one HBM round trip per element (the serial version measured
+  // 6.7 us for 2.6k params: pure latency)
+  constexpr int U = 4, STEP = 256 * U;
+  float g[U], mi_[U], vi_[U], p_[U];
+  auto load_batch = [&](int base) {
+    #pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int i = base + u * 256;
+      if (i < NPARAM) {
+        g[u] = grads[i];
+        mi_[u] = m[i];
+        vi_[u] = v[i];
+        p_[u] = master[i];
+      }
+    }
+  };
+  // Thread 0's chain (the step counter's round trip, two pow expansions, the
+  // LDS write) stands in front of the barrier. Every thread's first batch of
+  // loads goes out before it, thread 0's behind its counter load, so the
+  // chain runs beside them instead of in front of them.
+  int t = 0;
+  if (threadIdx.x == 0) t = *t_dev + 1;
+  int base = (int)threadIdx.x;
+  load_batch(base);
   if (threadIdx.x == 0) {
-    const int t = ++(*t_dev);
+    *t_dev = t;
     adam_bias_corr(beta1, beta2, (float)t, corr1, corr2);
   }
   __syncthreads();
-  // batch 4 strided elements' loads per iteration so the g/m/v/master
-  // reads overlap instead of serializing one HBM round trip per element
-  // (the serial version measured 6.7 µs for 2.6k params — pure latency)
-  for (int base = (int)threadIdx.x; base < NPARAM; base += 256 * 4) {
-    float g[4], mi_[4], vi_[4], p_[4];
-    int idx[4], n = 0;
+  for (;;) {
     #pragma unroll
-    for (int u = 0; u < 4; ++u) {
+    for (int u = 0; u < U; ++u) {
       const int i = base + u * 256;
       if (i < NPARAM) {
-        idx[n] = i;
-        g[n] = grads[i];
-        mi_[n] = m[i];
-        vi_[n] = v[i];
-        p_[n] = master[i];
-        ++n;
-      }
-    }
-    #pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      if (u < n) {
         float p = p_[u], mi = mi_[u], vi = vi_[u];
         adam_update(p, mi, vi, g[u], lr, beta1, beta2, eps, corr1, corr2);
-        const int i = idx[u];
         m[i] = mi;
         v[i] = vi;
         master[i] = p;
@@ -1112,6 +1186,9 @@ adam_step_kernel(float* __restrict__ master, u16* __restrict__ bfmirror,
         if (wimg) wimg_write(wimg, i, wb);
       }
     }
+    base += STEP;
+    if (base >= NPARAM) break;
+    load_batch(base);
   }
 }
 
