@@ -21,12 +21,14 @@ ext = CUDAExtension(
         "unionml_amd/ops/hip/tabular_kernels.hip",
         "unionml_amd/ops/hip/tabular_gen.hip",
         "unionml_amd/ops/hip/tabular_eval.hip",
+        "unionml_amd/ops/hip/tabular_shuffle.hip",
     ],
     # editing a shared header rebuilds the extension
     depends=[
         "unionml_amd/ops/hip/tabular_common.h",
         "unionml_amd/ops/hip/tabular_gen_tiles.h",
         "unionml_amd/ops/hip/tabular_launch.h",
+        "unionml_amd/ops/hip/tabular_shuffle.h",
     ],
     extra_compile_args={
         "cxx": ["-O3", "-std=c++17"],

@@ -63,6 +63,8 @@ def trainer(
     validation_fraction: float = 0.0,
     patience: int = 0,
     restore_best: bool = False,
+    shuffle: bool = False,
+    shuffle_seed: int = 0,
 ) -> TabularMLP:
     """Stage features into HBM (pinned async H2D), fit the standardizer,
     then run the fused-kernel minibatch loop. Under DP each rank gets a
@@ -93,6 +95,8 @@ def trainer(
         validation=validation,
         patience=patience or None,
         restore_best=restore_best,
+        shuffle=shuffle,
+        shuffle_seed=shuffle_seed,
     )
     return clf
 

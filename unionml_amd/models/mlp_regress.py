@@ -73,6 +73,8 @@ def trainer(
     validation_fraction: float = 0.0,
     patience: int = 0,
     restore_best: bool = False,
+    shuffle: bool = False,
+    shuffle_seed: int = 0,
 ) -> TabularMLPRegressor:
     """Stage features and targets into HBM, fit BOTH standardizers (the
     network learns standardized targets), then run the fused-kernel
@@ -103,6 +105,8 @@ def trainer(
         validation=validation,
         patience=patience or None,
         restore_best=restore_best,
+        shuffle=shuffle,
+        shuffle_seed=shuffle_seed,
     )
     return reg
 

@@ -1,12 +1,13 @@
 // Torch bindings for the CDNA4 tabular hot-path kernels
-// (tabular_kernels.hip, tabular_gen.hip, tabular_eval.hip; launchers and
-// layout constants: tabular_launch.h). All launches go to the current torch
+// (tabular_kernels.hip, tabular_gen.hip, tabular_eval.hip, tabular_shuffle.hip;
+// launchers and layout constants: tabular_launch.h, tabular_shuffle.h). All launches go to the current torch
 // stream so they compose with torch.cuda.graphs capture and RCCL work.
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
 #include "tabular_launch.h"
+#include "tabular_shuffle.h"
 
 namespace {
 
@@ -524,7 +525,133 @@ void mlp_eval_reg_gen(torch::Tensor Xbf, torch::Tensor Yt, int64_t hid,
   gen_launched(rc, "mlp_eval_reg_gen", a, targets);
 }
 
+// ---------------------------------------------------------------------------
+// shuffled epochs (tabular_shuffle.hip): gather the staged rows by the keyed
+// permutation of tabular_shuffle.h
+// ---------------------------------------------------------------------------
+
+namespace {
+
+// the bytes a contiguous tensor occupies
+struct Span {
+  const char* name;
+  uintptr_t lo, hi;
+};
+
+Span span_of(const torch::Tensor& t, const char* name) {
+  const uintptr_t lo = reinterpret_cast<uintptr_t>(t.data_ptr());
+  return {name, lo, lo + (uintptr_t)t.numel() * (uintptr_t)t.element_size()};
+}
+
+void check_disjoint(const Span& a, const Span& b) {
+  TORCH_CHECK(a.hi <= b.lo || b.hi <= a.lo, a.name, " and ", b.name,
+              " must not share storage");
+}
+
+// A shuffle's arguments, either head: all but the per-row targets. -> N
+struct ShuffleCall {
+  int64_t N;
+  unsigned seed;
+  int* perm_out;
+};
+
+ShuffleCall shuffle_args(const torch::Tensor& Xbf, const torch::Tensor& y,
+                         const char* y_name, const torch::Tensor& Xs,
+                         const torch::Tensor& ys, const char* ys_name,
+                         const torch::Tensor& t_dev, int64_t seed,
+                         const c10::optional<torch::Tensor>& perm_out) {
+  const int64_t N = check_rows(Xbf, torch::kBFloat16, "Xbf");
+  const int64_t inp = Xbf.size(1);
+  TORCH_CHECK(inp % 32 == 0, "Xbf must be [N][inp], inp a multiple of 32, is ",
+              Xbf.sizes());
+  check_aligned16(Xbf, "Xbf");
+  check(Xs, torch::kBFloat16, "Xs");
+  TORCH_CHECK(Xs.dim() == 2 && Xs.size(0) >= N && Xs.size(1) == inp,
+              "Xs must be [>= ", N, "][", inp, "], is ", Xs.sizes());
+  check_aligned16(Xs, "Xs");
+  check_n(t_dev, torch::kInt32, "t_dev", 1);
+  TORCH_CHECK(seed >= 0 && seed <= (int64_t)UINT32_MAX,
+              "seed must be in [0, 2^32), is ", seed);
+  int* perm = opt_ptr<int>(perm_out, torch::kInt32, "perm_out", N);
+  // the kernel reads a source row while another wave writes a destination
+  // row: no destination may alias a source or another destination
+  std::vector<Span> src{span_of(Xbf, "Xbf"), span_of(y, y_name),
+                        span_of(t_dev, "t_dev")};
+  std::vector<Span> dst{span_of(Xs, "Xs"), span_of(ys, ys_name)};
+  if (perm_out.has_value()) dst.push_back(span_of(*perm_out, "perm_out"));
+  for (size_t i = 0; i < dst.size(); ++i) {
+    for (const Span& s : src) check_disjoint(s, dst[i]);
+    for (size_t j = i + 1; j < dst.size(); ++j) check_disjoint(dst[i], dst[j]);
+  }
+  return {N, (unsigned)seed, perm};
+}
+
+}  // namespace
+
+void shuffle_rows(torch::Tensor Xbf, torch::Tensor y, torch::Tensor Xs,
+                  torch::Tensor ys, torch::Tensor t_dev, int64_t seed,
+                  c10::optional<torch::Tensor> perm_out = c10::nullopt) {
+  check_rows(Xbf, torch::kBFloat16, "Xbf");   // N, before the targets' counts
+  check_n(y, torch::kInt32, "y", Xbf.size(0), true);
+  check_n(ys, torch::kInt32, "ys", Xbf.size(0));
+  const ShuffleCall a = shuffle_args(Xbf, y, "y", Xs, ys, "ys", t_dev, seed, perm_out);
+  const int rc = launch_shuffle_rows(
+      bf16_ptr(Xbf), y.data_ptr<int>(), bf16_mut_ptr(Xs), ys.data_ptr<int>(),
+      a.perm_out, t_dev.data_ptr<int>(), a.seed, a.N, (int)Xbf.size(1),
+      current_stream());
+  TORCH_CHECK(rc == 0, "shuffle_rows: arguments outside the kernel's range");
+}
+
+void shuffle_rows_reg(torch::Tensor Xbf, torch::Tensor Yt, torch::Tensor Xs,
+                      torch::Tensor Yts, torch::Tensor t_dev, int64_t seed,
+                      c10::optional<torch::Tensor> perm_out = c10::nullopt) {
+  const int64_t N = check_rows(Xbf, torch::kBFloat16, "Xbf");
+  check(Yt, torch::kFloat32, "Yt");
+  TORCH_CHECK(Yt.dim() == 2 && Yt.size(0) == N &&
+                  (Yt.size(1) == 16 || Yt.size(1) == 32),
+              "Yt must be [", N, "][cpad = 16 or 32] staged targets, is ", Yt.sizes());
+  check_aligned16(Yt, "Yt");
+  check(Yts, torch::kFloat32, "Yts");
+  TORCH_CHECK(Yts.dim() == 2 && Yts.size(0) >= N && Yts.size(1) == Yt.size(1),
+              "Yts must be [>= ", N, "][", Yt.size(1), "], is ", Yts.sizes());
+  check_aligned16(Yts, "Yts");
+  const ShuffleCall a =
+      shuffle_args(Xbf, Yt, "Yt", Xs, Yts, "Yts", t_dev, seed, perm_out);
+  const int rc = launch_shuffle_rows_reg(
+      bf16_ptr(Xbf), Yt.data_ptr<float>(), bf16_mut_ptr(Xs), Yts.data_ptr<float>(),
+      a.perm_out, t_dev.data_ptr<int>(), a.seed, a.N, (int)Xbf.size(1),
+      (int)Yt.size(1), current_stream());
+  TORCH_CHECK(rc == 0, "shuffle_rows_reg: arguments outside the kernel's range");
+}
+
+// The permutation as the HOST compiles tabular_shuffle.h: src[i] for every
+// i < N, an int32 CPU tensor. No device involved; tests hold it equal to
+// reference.shuffle_perm and to the kernel's perm_out.
+torch::Tensor shuffle_perm_host(int64_t N, int64_t seed, int64_t t) {
+  TORCH_CHECK(N >= 1 && N <= INT_MAX, "N must be 1..INT_MAX, is ", N);
+  TORCH_CHECK(seed >= 0 && seed <= (int64_t)UINT32_MAX,
+              "seed must be in [0, 2^32), is ", seed);
+  TORCH_CHECK(t >= INT_MIN && t <= INT_MAX, "t must fit an int32, is ", t);
+  torch::Tensor out = torch::empty({N}, torch::dtype(torch::kInt32));
+  const ShufflePerm perm((unsigned)N, (unsigned)seed, (unsigned)(int)t);
+  int* p = out.data_ptr<int>();
+  for (int64_t i = 0; i < N; ++i) p[i] = (int)perm((unsigned)i);
+  return out;
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("shuffle_rows", &shuffle_rows,
+        "Xs[i] = Xbf[src], ys[i] = y[src] (int32 labels), src = P(i; N, seed, "
+        "t_dev[0]) the keyed permutation; perm_out[i] = src when given",
+        py::arg("Xbf"), py::arg("y"), py::arg("Xs"), py::arg("ys"),
+        py::arg("t_dev"), py::arg("seed"), py::arg("perm_out") = c10::nullopt);
+  m.def("shuffle_rows_reg", &shuffle_rows_reg,
+        "shuffle_rows over staged regression targets Yt [N][cpad] fp32",
+        py::arg("Xbf"), py::arg("Yt"), py::arg("Xs"), py::arg("Yts"),
+        py::arg("t_dev"), py::arg("seed"), py::arg("perm_out") = c10::nullopt);
+  m.def("shuffle_perm_host", &shuffle_perm_host,
+        "the keyed permutation of [0, N) evaluated on the host, int32 [N]",
+        py::arg("N"), py::arg("seed"), py::arg("t"));
   // evaluation record layout (tabular_launch.h EVAL_REC_*), fp32 entries
   m.attr("EVAL_REC_LOSS") = EVAL_REC_LOSS;
   m.attr("EVAL_REC_CORRECT") = EVAL_REC_CORRECT;      // int32 bits

@@ -487,3 +487,69 @@ def adam_step(
     eps: float = 1e-8,
 ) -> None:
     adam_step_g(DIGITS, master, bfmirror, grads, m, v, t, lr, beta1, beta2, eps)
+
+
+# ---------------------------------------------------------------------------
+# shuffled epochs: the keyed permutation of [0, N) (hip/tabular_shuffle.h holds
+# the device copy; tests hold the two equal)
+# ---------------------------------------------------------------------------
+
+SHUFFLE_ROUNDS = 6
+SHUFFLE_GOLDEN = 0x9E3779B9
+_M32 = 0xFFFFFFFF
+
+
+def _fmix32(h):
+    """murmur3's 32-bit finalizer on an int, or elementwise on an int64
+    tensor of values below 2**32 (int64 products wrap mod 2**64, the low 32
+    bits are the uint32 product)."""
+    h = h ^ (h >> 16)
+    h = (h * 0x85EBCA6B) & _M32
+    h = h ^ (h >> 13)
+    h = (h * 0xC2B2AE35) & _M32
+    return h ^ (h >> 16)
+
+
+def shuffle_half_bits(n: int) -> int:
+    """Half the bit width of the Feistel domain that covers [0, n):
+    max(1, ceil(ceil(log2 n) / 2)), so the domain 4**half is in [n, 4n)
+    (n = 1: the smallest domain, 4)."""
+    return max(1, ((n - 1).bit_length() + 1) // 2)
+
+
+def shuffle_round_keys(seed: int, t: int) -> Tuple[int, ...]:
+    """rk_r = fmix32(seed ^ fmix32(t ^ (GOLDEN * (r + 1) mod 2**32)))."""
+    seed, t = seed & _M32, t & _M32
+    return tuple(
+        _fmix32(seed ^ _fmix32(t ^ ((SHUFFLE_GOLDEN * (r + 1)) & _M32)))
+        for r in range(SHUFFLE_ROUNDS)
+    )
+
+
+def _shuffle_feistel(x: torch.Tensor, half: int, keys) -> torch.Tensor:
+    mask = (1 << half) - 1
+    L, R = x >> half, x & mask
+    for rk in keys:
+        L, R = R, L ^ (_fmix32(R ^ rk) & mask)
+    return (L << half) | R
+
+
+def shuffle_perm(n: int, seed: int, t: int) -> torch.Tensor:
+    """src[i] = P(i; n, seed, t) for every i in [0, n): a bijection of
+    [0, n), int64 on the CPU. A balanced 6-round Feistel network over
+    2 * half bits, cycle-walked into [0, n): integer-only, stateless, the
+    function the shuffle kernel evaluates per row. ``t`` is the Adam step
+    counter at the start of the epoch; it and ``seed`` are taken mod 2**32.
+
+    The walk ends: the network is a bijection of its domain and the start
+    is below n, so the start's cycle comes back below n after at most
+    domain - n + 1 applications."""
+    if not 1 <= n <= 2**31 - 1:
+        raise ValueError(f"shuffle_perm needs 1 <= n <= INT_MAX, is {n}")
+    half, keys = shuffle_half_bits(n), shuffle_round_keys(seed, t)
+    x = _shuffle_feistel(torch.arange(n, dtype=torch.int64), half, keys)
+    while True:
+        out = (x >= n).nonzero().squeeze(1)
+        if not out.numel():
+            return x
+        x[out] = _shuffle_feistel(x[out], half, keys)

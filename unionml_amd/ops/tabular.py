@@ -114,6 +114,9 @@ class TabularMLP:
         self._eval_one = None
         self._eval_wimg = None
         self._val_buf = None
+        # shuffled epochs: the destination buffers (Xs, ys) the shuffle
+        # launch gathers the staged rows into; built on first use
+        self._shuf = None
         #: one evaluation record per epoch of the last
         #: train_epochs(validation=...), a CPU tensor [epochs run][record]
         self.val_history = None
@@ -327,6 +330,43 @@ class TabularMLP:
         last loss into ``loss_out``."""
         self._launch_step(Xbf, y, invBtot, lr, loss_out)
 
+    # -- shuffled epochs -------------------------------------------------------
+
+    def _ensure_shuffle(self, Xbf, y):
+        """The destination buffers of a shuffled epoch, shaped like the
+        staged inputs."""
+        buf = self._shuf
+        if buf is None or any(
+            (b.shape, b.dtype, b.device) != (t.shape, t.dtype, t.device)
+            for b, t in zip(buf, (Xbf, y))
+        ):
+            self._shuf = (torch.empty_like(Xbf), torch.empty_like(y))
+            # a captured epoch holds the old buffers' addresses
+            self._graph = self._graph_key = None
+        return self._shuf
+
+    def _shuffle_kernel(self, ext, Xbf, y, Xs, ys, seed: int):
+        """The shuffle launch, by head."""
+        ext.shuffle_rows(Xbf, y, Xs, ys, self.t_dev, seed)
+
+    def _shuffled(self, Xbf, y, seed: int):
+        """This epoch's rows: the staged originals gathered by the keyed
+        permutation P(.; N, seed, t_dev) (reference.shuffle_perm). On the
+        device one launch into the model's buffers, which reads t_dev when
+        it runs, so a replayed epoch re-keys itself; on the CPU the
+        reference permutation."""
+        if self.use_hip:
+            Xs, ys = self._shuf
+            self._shuffle_kernel(hip_ext(), Xbf, y, Xs, ys, seed)
+            return Xs, ys
+        perm = ref.shuffle_perm(Xbf.shape[0], seed, int(self.t_dev.item()))
+        return Xbf[perm], y[perm]
+
+    def _shuffle_key(self, seed: int):
+        """What a captured shuffled epoch bakes in besides the sources'
+        addresses (already in the key): the flag, the seed, the buffers."""
+        return ("shuffle", seed) + tuple(b.data_ptr() for b in self._shuf)
+
     def _run_epochs(self, run_epoch, epochs: int, key, use_graph: bool,
                     after_epoch=None) -> float:
         """Device epoch driver: one eager warmup epoch (also warms the
@@ -359,7 +399,7 @@ class TabularMLP:
         return float(self.grads[self.g.nparam].item())
 
     def _train_epochs_fused(self, Xbf, y, batches, *, epochs, lr, use_graph,
-                            val=None) -> float:
+                            val=None, shuffle_seed=None) -> float:
         g = self.g
         self._ensure_slabs(
             max(
@@ -370,9 +410,11 @@ class TabularMLP:
         loss_out = self.grads[g.nparam : g.nparam + 1]
 
         def run_epoch():
+            Xe, ye = (Xbf, y) if shuffle_seed is None else self._shuffled(
+                Xbf, y, shuffle_seed)
             for off, bs in batches:
                 self._fused_adam_step(
-                    Xbf[off : off + bs], y[off : off + bs], 1.0 / bs, lr, loss_out
+                    Xe[off : off + bs], ye[off : off + bs], 1.0 / bs, lr, loss_out
                 )
             if val is not None:
                 # same stream, after the epoch's last step: still one chain
@@ -381,6 +423,8 @@ class TabularMLP:
         # the capture bakes in every batch's offset, row count and 1/bs:
         # the key is the batch list itself, not its length
         key = ("fused", tuple(batches), lr, Xbf.data_ptr(), y.data_ptr())
+        if shuffle_seed is not None:
+            key += self._shuffle_key(shuffle_seed)
         if val is None:
             return self._run_epochs(run_epoch, epochs, key, use_graph)
         # ... and the validation rows, the history (its row count is the
@@ -405,6 +449,8 @@ class TabularMLP:
         patience: Optional[int] = None,
         min_delta: float = 0.0,
         restore_best: bool = False,
+        shuffle: bool = False,
+        shuffle_seed: int = 0,
     ) -> float:
         """Minibatch Adam training over the staged (bf16) features.
 
@@ -418,8 +464,31 @@ class TabularMLP:
         loss has not improved by more than ``min_delta`` for that many
         epochs, ``restore_best`` puts back the weights and optimizer state
         of the best epoch; either costs one host sync per epoch.
+
+        ``shuffle=True`` trains every epoch on a fresh permutation of the
+        rows: one device launch at the head of the epoch gathers ``Xbf`` and
+        ``y`` into buffers the model owns, inside the captured epoch. The
+        order is ``reference.shuffle_perm(N, shuffle_seed, t)`` with ``t``
+        the Adam step counter at the start of the epoch, so it depends on
+        nothing but the row count, the seed and the checkpointed counter:
+        a resumed run continues the same sequence of orders. Validation
+        rows are never shuffled.
         """
         g = self.g
+        if shuffle:
+            if engine == "persistent":
+                raise ValueError(
+                    "shuffle is not supported by engine='persistent': the "
+                    "persistent kernel runs all epochs in one launch"
+                )
+            if world_size > 1:
+                raise ValueError(
+                    "shuffle is not supported under data parallel (world_size > 1)"
+                )
+            if not 0 <= shuffle_seed < 2**32:
+                raise ValueError(
+                    f"shuffle_seed must be in [0, 2**32), is {shuffle_seed}"
+                )
         y = self._prep_targets(y)
         val = None
         if validation is None:
@@ -443,6 +512,9 @@ class TabularMLP:
             (off, min(batch_size, n - off)) for off in range(0, n, batch_size)
         ]
         allreduce = world_size > 1
+        seed = int(shuffle_seed) if shuffle and n else None
+        if seed is not None and self.use_hip:
+            self._ensure_shuffle(Xbf, y)
 
         # single-GPU flagship: the fully-fused step kernel (fwd+bwd +
         # cross-WG slab reduction + Adam in ONE launch), with the epoch's
@@ -470,20 +542,23 @@ class TabularMLP:
                     return float(loss_out.item())
             if val is None:
                 return self._train_epochs_fused(
-                    Xbf, y, batches, epochs=epochs, lr=lr, use_graph=use_graph
+                    Xbf, y, batches, epochs=epochs, lr=lr, use_graph=use_graph,
+                    shuffle_seed=seed,
                 )
             loss = self._train_epochs_fused(
-                Xbf, y, batches, epochs=epochs, lr=lr, use_graph=use_graph, val=val
+                Xbf, y, batches, epochs=epochs, lr=lr, use_graph=use_graph, val=val,
+                shuffle_seed=seed,
             )
             val.finish()
             return loss
 
         def run_epoch():
             last = None
+            Xe, ye = (Xbf, y) if seed is None else self._shuffled(Xbf, y, seed)
             for off, bs in batches:
                 last = self._step(
-                    Xbf[off : off + bs],
-                    y[off : off + bs],
+                    Xe[off : off + bs],
+                    ye[off : off + bs],
                     1.0 / (bs * world_size),
                     lr,
                     allreduce,
@@ -502,6 +577,8 @@ class TabularMLP:
             return float(loss.item()) if loss is not None else float("nan")
 
         key = (n, batch_size, world_size, lr, Xbf.data_ptr(), y.data_ptr())
+        if seed is not None:
+            key += self._shuffle_key(seed)
         return self._run_epochs(run_epoch, epochs, key, use_graph=True)
 
     # -- evaluation ------------------------------------------------------------
@@ -659,6 +736,7 @@ class TabularMLP:
         d["slabs"] = d["counter"] = None
         d["_graph"] = d["_graph_key"] = None
         d["_eval_part"] = d["_eval_one"] = d["_eval_wimg"] = d["_val_buf"] = None
+        d["_shuf"] = None
         d["wimg"] = None
         d["device"] = str(self.device)
         for k, v in list(d.items()):
@@ -675,6 +753,7 @@ class TabularMLP:
         for k in ("_eval_part", "_eval_one", "_eval_wimg", "_val_buf", "val_history"):
             state.setdefault(k, None)                     # pre-evaluation pickles
         state.setdefault("_val_n", 0)
+        state.setdefault("_shuf", None)                   # pre-shuffle pickles
         self.__dict__.update(state)
         self.device = device
         self.use_hip = device.type == "cuda"
@@ -903,6 +982,9 @@ class TabularMLPRegressor(TabularMLP):
             Xbf, Yt, g.hid, g.classes, rpw, self.wimg, self.master,
             self.slabs, invBtot,
         )
+
+    def _shuffle_kernel(self, ext, Xbf, Yt, Xs, Yts, seed: int):
+        ext.shuffle_rows_reg(Xbf, Yt, Xs, Yts, self.t_dev, seed)
 
     def _ref_step(self, Xbf, Yt, invBtot: float):
         ref.mlp_step_reg_g(

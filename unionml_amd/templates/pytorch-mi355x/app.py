@@ -55,14 +55,18 @@ def trainer(
     epochs: int = 30,
     batch_size: int = 512,
     lr: float = 2e-3,
+    shuffle: bool = False,
+    shuffle_seed: int = 0,
 ) -> TabularMLP:
     stager = get_stager(clf.device)
     X = stager.to_device(features.to_numpy().astype(np.float32))
     y = stager.to_device(target.squeeze().to_numpy().astype(np.int32))
     clf.fit_standardizer(X)
     Xbf = clf.stage(X)
+    # shuffle=True reorders the rows every epoch on the device (single GPU)
     clf.train_epochs(
-        Xbf, y, epochs=epochs, batch_size=batch_size, lr=lr, world_size=get_world_size()
+        Xbf, y, epochs=epochs, batch_size=batch_size, lr=lr, world_size=get_world_size(),
+        shuffle=shuffle, shuffle_seed=shuffle_seed,
     )
     return clf
 
