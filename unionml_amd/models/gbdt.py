@@ -3,10 +3,13 @@
 sklearn's HistGradientBoostingClassifier on the digits shape through
 the same decorator API (the reference's sklearn surface is exactly this
 kind of estimator; its quickstart uses LogisticRegression —
-tests/integration/sklearn_app/quickstart.py). Trees don't map to MFMA,
-so this app runs CPU-side estimators by design; it exists so the
-framework's "any sklearn estimator" path has a first-class, tested
-boosting example with warm-start iteration control.
+tests/integration/sklearn_app/quickstart.py). Trees don't map to MFMA, so
+the app fits on the CPU, predicts on the device: with a GPU present the
+predictor (and thereby the evaluator) scores through
+:class:`unionml_amd.ops.forest.ForestPredictor`, whose kernel reproduces the
+estimator's fp64 raw scores bit for bit. It exists so the framework's "any
+sklearn estimator" path has a first-class, tested boosting example with
+warm-start iteration control.
 """
 
 from typing import List
@@ -16,6 +19,8 @@ import pandas as pd
 from sklearn.ensemble import HistGradientBoostingClassifier
 
 from unionml_amd import Dataset, Model
+from unionml_amd.ops import hip_available
+from unionml_amd.ops.forest import ForestPredictor
 
 FEATURES = [f"p{i}" for i in range(64)]
 
@@ -63,8 +68,39 @@ def trainer(
     return clf.fit(features, target.squeeze())
 
 
+class _ForestCache:
+    """The packed forest of a fitted estimator, kept on the estimator object.
+    Valid while the estimator holds the same list of iterations at the same
+    length (a refit makes a new list, a warm start extends it). Pickles as an
+    empty cache, so that a saved artifact holds no device memory."""
+
+    def __init__(self):
+        self.iterations, self.count, self.forest = None, 0, None
+
+    def __reduce__(self):
+        return (_ForestCache, ())
+
+    def get(self, clf) -> ForestPredictor:
+        its = clf._predictors
+        if self.iterations is not its or self.count != len(its):
+            self.forest = ForestPredictor.from_sklearn(clf)
+            self.iterations, self.count = its, len(its)
+        return self.forest
+
+
+def device_forest(clf: HistGradientBoostingClassifier) -> ForestPredictor:
+    """The estimator's device-resident forest, built once per fit."""
+    cache = getattr(clf, "_unionml_forest", None)
+    if cache is None:
+        cache = clf._unionml_forest = _ForestCache()
+    return cache.get(clf)
+
+
 @model.predictor
 def predictor(clf: HistGradientBoostingClassifier, features: pd.DataFrame) -> List[int]:
+    if hip_available():
+        X = features.to_numpy(dtype=np.float32)
+        return [int(x) for x in device_forest(clf).predict(X)]
     return [int(x) for x in clf.predict(features)]
 
 

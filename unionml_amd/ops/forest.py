@@ -1,0 +1,210 @@
+"""Device-resident inference of a fitted gradient-boosted forest.
+
+``ForestPredictor.from_sklearn(est)`` packs a fitted
+``HistGradientBoostingClassifier`` / ``HistGradientBoostingRegressor`` into
+flat tensors (the format of ``hip/forest.h``) and scores rows through
+``forest_predict_kernel``. The kernel makes sklearn's comparisons and
+sklearn's fp64 additions in sklearn's order, so ``decision_function`` equals
+``est.decision_function`` bit for bit (docs/kernels.md "Forest inference").
+On a machine without a GPU the same packed arrays are walked by a plain
+vectorised fp64 traversal; on a GPU machine a missing extension is the usual
+``KernelExtensionNotBuilt``.
+"""
+
+from collections import deque
+
+import numpy as np
+import torch
+
+from unionml_amd.ops import hip_ext
+
+# the Python copy of hip/forest.h (a GPU test holds the two equal)
+MAX_CLASSES = 32
+MAX_FEATURES = 2048
+CHUNK_NODES = 2048          # the most nodes one tree may have: one LDS chunk
+CHUNK_TREES = 256
+MIN_ROWS, MAX_ROWS = 4, 2048
+BLOCK, MAX_ITEMS = 256, 8
+TILE_BYTES = 80 * 1024 - (CHUNK_NODES * 16 + CHUNK_TREES * 4 + MAX_CLASSES * 8)
+
+NODE_DTYPE = np.dtype([("thr", "<f4"), ("meta", "<u4"), ("value", "<f8")])
+META_LEFT_SHIFT, META_MISSING_LEFT = 16, 1 << 31
+
+
+def rd32(t):
+    """fp64 thresholds rounded to fp32 towards -inf: for every fp32 ``x``,
+    ``x <= t`` (in fp64) holds exactly when ``x <= rd32(t)`` (in fp32)."""
+    t = np.asarray(t, dtype=np.float64)
+    with np.errstate(over="ignore"):
+        f = t.astype(np.float32)
+    up = f.astype(np.float64) > t          # the conversion rounded up
+    return np.where(up, np.nextafter(f, np.float32(-np.inf)), f).astype(np.float32)
+
+
+def rows_per_wg(n_features: int, n_scores: int) -> int:
+    """Rows per workgroup: the largest power of two whose fp32 tile (odd row
+    stride) fits the carve and whose rows x classes fit 8 items a thread."""
+    if not (1 <= n_features <= MAX_FEATURES and 1 <= n_scores <= MAX_CLASSES):
+        return 0
+    R = MAX_ROWS
+    while R > MIN_ROWS and (R * (n_features | 1) * 4 > TILE_BYTES
+                            or R * n_scores > BLOCK * MAX_ITEMS):
+        R //= 2
+    return R
+
+
+def _pack_tree(nodes):
+    """One sklearn tree -> packed nodes, renumbered breadth-first so that a
+    node's children are adjacent; a leaf points at itself behind thr = +inf
+    with the missing-goes-left bit set."""
+    order, queue = [], deque([0])
+    while queue:
+        i = queue.popleft()
+        order.append(i)
+        if not nodes["is_leaf"][i]:
+            queue.extend((int(nodes["left"][i]), int(nodes["right"][i])))
+    order = np.asarray(order)
+    new_of = np.empty(len(nodes), dtype=np.int64)
+    new_of[order] = np.arange(len(order))
+    src = nodes[order]
+    leaf = src["is_leaf"].astype(bool)
+    out = np.zeros(len(order), dtype=NODE_DTYPE)
+    out["thr"] = np.where(leaf, np.float32(np.inf), rd32(src["num_threshold"]))
+    left = np.where(leaf, np.arange(len(order)), new_of[src["left"]])
+    assert np.all(leaf | (new_of[src["right"]] == left + 1))
+    missing_left = leaf | src["missing_go_to_left"].astype(bool)
+    feature = np.where(leaf, 0, src["feature_idx"])
+    out["meta"] = (feature.astype(np.uint32) | (left.astype(np.uint32) << META_LEFT_SHIFT)
+                   | np.where(missing_left, np.uint32(META_MISSING_LEFT), np.uint32(0)))
+    out["value"] = np.where(leaf, src["value"], 0.0)
+    return out
+
+
+class ForestPredictor:
+    """A packed forest on one device. Build with :meth:`from_sklearn`."""
+
+    def __init__(self, nodes, tree_first, baseline, n_features, classes=None,
+                 identity_link=True, device=None):
+        if device is None:
+            device = "cuda" if torch.cuda.is_available() else "cpu"
+        self.device = torch.device(device)
+        self.n_features = int(n_features)
+        self.n_scores = int(len(baseline))
+        self.n_trees = int(len(tree_first) - 1)
+        self.max_tree_nodes = int(np.diff(tree_first).max())
+        self.rows_per_wg = rows_per_wg(self.n_features, self.n_scores)
+        self.classes_ = None if classes is None else np.asarray(classes)
+        self.identity_link = bool(identity_link)
+        self._nodes_np, self._first_np, self._baseline_np = nodes, tree_first, baseline
+        self._ext = None
+        if self.device.type == "cuda":
+            self._ext = hip_ext(required=True)
+            self._nodes = torch.from_numpy(nodes.view("<i4").reshape(-1, 4)).to(self.device)
+            self._first = torch.from_numpy(tree_first).to(self.device)
+            self._baseline = torch.from_numpy(baseline).to(self.device)
+
+    @classmethod
+    def from_sklearn(cls, est, device=None):
+        predictors = est._predictors
+        K = len(predictors[0])
+        if not 1 <= K <= MAX_CLASSES:
+            raise ValueError(f"{K} trees per iteration: the kernel takes 1..{MAX_CLASSES}")
+        F = int(est.n_features_in_)
+        if F > MAX_FEATURES:
+            raise ValueError(f"{F} features: the row tile takes at most {MAX_FEATURES}")
+        trees = [tree.nodes for iteration in predictors for tree in iteration]
+        if any(t["is_categorical"].any() for t in trees):
+            raise ValueError("categorical splits are not supported by the forest kernel")
+        largest = max(len(t) for t in trees)
+        if largest > CHUNK_NODES:
+            raise ValueError(f"a tree has {largest} nodes: one LDS chunk holds {CHUNK_NODES}")
+        if sum(len(t) for t in trees) > 1 << 30:
+            raise ValueError("the forest has more than 2^30 nodes")
+        nodes = np.concatenate([_pack_tree(t) for t in trees])
+        tree_first = np.concatenate([[0], np.cumsum([len(t) for t in trees])]).astype(np.int32)
+        # sklearn starts from zeros + baseline
+        baseline = 0.0 + np.asarray(est._baseline_prediction, dtype=np.float64).reshape(-1)
+        assert len(baseline) == K
+        return cls(nodes, tree_first, baseline, F, classes=getattr(est, "classes_", None),
+                   identity_link=type(est._loss.link).__name__ == "IdentityLink",
+                   device=device)
+
+    # -- scoring ----------------------------------------------------------------
+
+    def _rows(self, X):
+        X = torch.as_tensor(np.asarray(X) if not torch.is_tensor(X) else X)
+        if X.dim() != 2 or X.shape[1] != self.n_features or not X.is_floating_point():
+            raise ValueError(f"X must be a float [B][{self.n_features}], is {tuple(X.shape)} "
+                             f"{X.dtype}")
+        return X.to(self.device, torch.float32).contiguous()
+
+    def _score(self, X, trees_per_chunk=0):
+        """-> (scores fp64 [B][K], class indices int32 [B]) on the device."""
+        X = self._rows(X)
+        B, K = X.shape[0], self.n_scores
+        scores = torch.empty(B, K, dtype=torch.float64, device=self.device)
+        labels = torch.empty(B, dtype=torch.int32, device=self.device)
+        if B == 0:
+            return scores, labels
+        if self._ext is not None:
+            self._ext.forest_predict(X, self._nodes, self._first, self._baseline,
+                                     self.max_tree_nodes, scores, labels, trees_per_chunk)
+            return scores, labels
+        s, _ = self._walk_cpu(X.numpy())
+        scores.copy_(torch.from_numpy(s))
+        idx = (s[:, 0] > 0) if K == 1 else s.argmax(axis=1)   # first of the largest
+        labels.copy_(torch.from_numpy(idx.astype(np.int32)))
+        return scores, labels
+
+    def _walk_cpu(self, X):
+        """The packed arrays walked on the host, tree by tree in the kernel's
+        order -> (scores fp64 [B][K], node visits, leaves included)."""
+        nodes, first, K = self._nodes_np, self._first_np, self.n_scores
+        thr, meta, value = nodes["thr"], nodes["meta"], nodes["value"]
+        B = X.shape[0]
+        rows = np.arange(B)
+        scores = np.tile(self._baseline_np, (B, 1))
+        visits = 0
+        for t in range(self.n_trees):
+            base = int(first[t])
+            idx = np.full(B, base)
+            while True:
+                m = meta[idx]
+                x = X[rows, m & 0xFFFF]
+                go_left = np.where(np.isnan(x), (m >> 31) != 0, x <= thr[idx])
+                nxt = base + ((m >> META_LEFT_SHIFT) & 0x7FFF) + np.where(go_left, 0, 1)
+                visits += int((nxt != idx).sum())
+                if np.array_equal(nxt, idx):
+                    break
+                idx = nxt
+            visits += B
+            scores[:, t % K] += value[idx]
+        return scores, visits
+
+    def decision_function(self, X, trees_per_chunk=0):
+        """Raw scores, fp64 ``[B][K]`` on the predictor's device: sklearn's
+        ``decision_function`` (``predict`` for an identity-link regressor) bit
+        for bit. ``trees_per_chunk`` caps the trees per LDS chunk (tests)."""
+        return self._score(X, trees_per_chunk)[0]
+
+    def predict(self, X, trees_per_chunk=0):
+        """Classifier: labels by the raw-score argmax (ties to the lowest
+        class; ``score > 0`` when binary) through ``classes_``, a numpy array.
+        Regressor: the values, fp64 ``[B]`` on the device."""
+        if self.classes_ is None:
+            if not self.identity_link:
+                raise ValueError("predict() of a regressor with a non-identity link is not "
+                                 "supported; decision_function() returns the raw scores")
+            return self._score(X, trees_per_chunk)[0][:, 0]
+        return self.classes_[self._score(X, trees_per_chunk)[1].cpu().numpy()]
+
+    def predict_proba(self, X):
+        """softmax (sigmoid when binary) of the raw scores, with torch on the
+        device; fp64 ``[B][n_classes]``."""
+        if self.classes_ is None:
+            raise ValueError("predict_proba() needs a classifier")
+        s = self.decision_function(X)
+        if self.n_scores == 1:
+            p = torch.sigmoid(s)
+            return torch.cat([1.0 - p, p], dim=1)
+        return torch.softmax(s, dim=1)

@@ -1,11 +1,13 @@
 // Torch bindings for the CDNA4 tabular hot-path kernels
-// (tabular_kernels.hip, tabular_gen.hip, tabular_eval.hip, tabular_shuffle.hip;
-// launchers and layout constants: tabular_launch.h, tabular_shuffle.h). All launches go to the current torch
+// (tabular_kernels.hip, tabular_gen.hip, tabular_eval.hip, tabular_shuffle.hip,
+// forest_predict.hip; launchers and layout constants: tabular_launch.h,
+// tabular_shuffle.h, forest.h). All launches go to the current torch
 // stream so they compose with torch.cuda.graphs capture and RCCL work.
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
+#include "forest.h"
 #include "tabular_launch.h"
 #include "tabular_shuffle.h"
 
@@ -639,7 +641,77 @@ torch::Tensor shuffle_perm_host(int64_t N, int64_t seed, int64_t t) {
   return out;
 }
 
+// ---------------------------------------------------------------------------
+// forest inference (forest_predict.hip): scores and labels of a packed
+// gradient-boosted forest (forest.h)
+// ---------------------------------------------------------------------------
+
+void forest_predict(torch::Tensor X, torch::Tensor nodes, torch::Tensor tree_first,
+                    torch::Tensor baseline, int64_t max_tree_nodes,
+                    torch::Tensor scores, torch::Tensor labels,
+                    int64_t trees_per_chunk = 0) {
+  const int64_t B = check_rows(X, torch::kFloat32, "X");
+  const int64_t F = X.size(1);
+  TORCH_CHECK(F <= FOREST_MAX_FEATURES, "X has ", F, " features, the row tile takes ",
+              FOREST_MAX_FEATURES);
+  check(baseline, torch::kFloat64, "baseline");
+  const int64_t K = baseline.numel();
+  TORCH_CHECK(baseline.dim() == 1 && K >= 1 && K <= FOREST_MAX_CLASSES,
+              "baseline must be [1 <= K <= ", FOREST_MAX_CLASSES, "], is ",
+              baseline.sizes());
+  check(nodes, torch::kInt32, "nodes");
+  TORCH_CHECK(nodes.dim() == 2 && nodes.size(1) == 4 && nodes.size(0) >= 1 &&
+                  nodes.size(0) <= (1 << 30),
+              "nodes must be [1 <= N <= 2^30][4] int32 (16-byte nodes), is ",
+              nodes.sizes());
+  check_aligned16(nodes, "nodes");
+  check(tree_first, torch::kInt32, "tree_first");
+  const int64_t T = tree_first.numel() - 1;
+  TORCH_CHECK(tree_first.dim() == 1 && T >= 1 && T <= (1 << 30) && T % K == 0 &&
+                  T <= nodes.size(0),
+              "tree_first must be [T + 1], T a positive multiple of K = ", K,
+              " and at most the node count ", nodes.size(0), ", is ",
+              tree_first.sizes());
+  TORCH_CHECK(max_tree_nodes >= 1 && max_tree_nodes <= FOREST_CHUNK_NODES,
+              "max_tree_nodes must be 1..", FOREST_CHUNK_NODES,
+              " (one tree must fit an LDS chunk), is ", max_tree_nodes);
+  TORCH_CHECK(trees_per_chunk >= 0 && trees_per_chunk <= INT_MAX,
+              "trees_per_chunk must be 0 (as many as fit) or positive, is ",
+              trees_per_chunk);
+  check(scores, torch::kFloat64, "scores");
+  TORCH_CHECK(scores.dim() == 2 && scores.size(0) >= B && scores.size(1) == K,
+              "scores must be [>= ", B, "][", K, "], is ", scores.sizes());
+  check_n(labels, torch::kInt32, "labels", B);
+  const Span outs[] = {span_of(scores, "scores"), span_of(labels, "labels")};
+  const Span ins[] = {span_of(X, "X"), span_of(nodes, "nodes"),
+                      span_of(tree_first, "tree_first"), span_of(baseline, "baseline")};
+  for (const Span& o : outs)
+    for (const Span& i : ins) check_disjoint(i, o);
+  check_disjoint(outs[0], outs[1]);
+  const int rc = launch_forest_predict(
+      X.data_ptr<float>(), (int)B, (int)F, (int)K,
+      reinterpret_cast<const ForestNode*>(nodes.data_ptr()), (int)nodes.size(0),
+      tree_first.data_ptr<int>(), (int)T, (int)max_tree_nodes, (int)trees_per_chunk,
+      baseline.data_ptr<double>(), scores.data_ptr<double>(), labels.data_ptr<int>(),
+      current_stream());
+  TORCH_CHECK(rc != -2, "forest_predict: could not raise the dynamic-LDS limit");
+  TORCH_CHECK(rc == 0, "forest_predict: arguments outside the kernel's range");
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("forest_predict", &forest_predict,
+        "scores[b][k] = baseline[k] + the leaves of trees k, K + k, ... in order "
+        "(fp64, sklearn's bits); labels[b] = argmax, or score > 0 at K = 1",
+        py::arg("X"), py::arg("nodes"), py::arg("tree_first"), py::arg("baseline"),
+        py::arg("max_tree_nodes"), py::arg("scores"), py::arg("labels"),
+        py::arg("trees_per_chunk") = 0);
+  m.def("forest_rows_per_wg",
+        [](int64_t F, int64_t K) { return forest_rows_per_wg((int)F, (int)K); },
+        "rows per workgroup of forest_predict (0: F or K out of range)",
+        py::arg("F"), py::arg("K"));
+  m.attr("FOREST_CHUNK_NODES") = FOREST_CHUNK_NODES;
+  m.attr("FOREST_CHUNK_TREES") = FOREST_CHUNK_TREES;
+  m.attr("FOREST_MAX_FEATURES") = FOREST_MAX_FEATURES;
   m.def("shuffle_rows", &shuffle_rows,
         "Xs[i] = Xbf[src], ys[i] = y[src] (int32 labels), src = P(i; N, seed, "
         "t_dev[0]) the keyed permutation; perm_out[i] = src when given",
