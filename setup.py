@@ -23,9 +23,11 @@ ext = CUDAExtension(
         "unionml_amd/ops/hip/tabular_eval.hip",
         "unionml_amd/ops/hip/tabular_shuffle.hip",
         "unionml_amd/ops/hip/forest_predict.hip",
+        "unionml_amd/ops/hip/bagged_forest_predict.hip",
     ],
     # editing a shared header rebuilds the extension
     depends=[
+        "unionml_amd/ops/hip/bagged_forest.h",
         "unionml_amd/ops/hip/forest.h",
         "unionml_amd/ops/hip/tabular_common.h",
         "unionml_amd/ops/hip/tabular_gen_tiles.h",

@@ -9,6 +9,12 @@ sklearn's fp64 additions in sklearn's order, so ``decision_function`` equals
 On a machine without a GPU the same packed arrays are walked by a plain
 vectorised fp64 traversal; on a GPU machine a missing extension is the usual
 ``KernelExtensionNotBuilt``.
+
+``BaggedForestPredictor`` does the same for ``RandomForest*``, ``ExtraTrees*``
+and single ``DecisionTree*`` / ``ExtraTree*`` estimators (the format of
+``hip/bagged_forest.h``, ``bagged_forest_predict_kernel``): ``predict_proba``
+/ ``predict`` equal sklearn's at ``n_jobs=None`` bit for bit. The module's
+``from_sklearn(est)`` returns the predictor that fits the estimator.
 """
 
 from collections import deque
@@ -208,3 +214,223 @@ class ForestPredictor:
             p = torch.sigmoid(s)
             return torch.cat([1.0 - p, p], dim=1)
         return torch.softmax(s, dim=1)
+
+
+# ---------------------------------------------------------------------------
+# bagged forests: random forests, extra-trees, single decision trees
+# ---------------------------------------------------------------------------
+
+# the Python copy of hip/bagged_forest.h (a GPU test holds the two equal)
+BAGGED_MAX_TREE_NODES = 1 << 20
+BAGGED_MIN_ROWS, BAGGED_MAX_ROWS = 4, 256
+BAGGED_MAX_ITEMS = 2048         # rows x values a leaf of one workgroup
+BAGGED_WALK_ITEMS = 2048        # rows x trees of one chunk
+BAGGED_CHUNK_TREES = 256
+BAGGED_TILE_BYTES = 80 * 1024 - (2048 * 8 + BAGGED_MAX_ITEMS * 8 + BAGGED_WALK_ITEMS * 4
+                                 + 2 * 2 * BAGGED_CHUNK_TREES * 4)
+
+# a leaf's "thr" holds its leaf_values row, so both fields are kept as bits
+BAGGED_NODE_DTYPE = np.dtype([("thr", "<u4"), ("meta", "<u4")])
+BAGGED_META_MISSING_LEFT, BAGGED_META_DIST_SHIFT = 1 << 11, 12
+
+
+def bagged_rows_per_wg(n_features: int, n_scores: int) -> int:
+    """Rows per workgroup of the bagged kernel: the largest power of two in
+    4..256 whose fp32 tile (odd row stride) fits the carve and whose rows x
+    values fit 2,048 sums."""
+    if not (1 <= n_features <= MAX_FEATURES and 1 <= n_scores <= MAX_CLASSES):
+        return 0
+    R = BAGGED_MAX_ROWS
+    while R > BAGGED_MIN_ROWS and (R * (n_features | 1) * 4 > BAGGED_TILE_BYTES
+                                   or R * n_scores > BAGGED_MAX_ITEMS):
+        R //= 2
+    return R
+
+
+def bagged_trees_per_chunk(rows: int, n_trees: int, cap: int = 0) -> int:
+    """Trees a workgroup that holds ``rows`` rows walks at once."""
+    rp = 1
+    while rp < rows:
+        rp *= 2
+    n = min(BAGGED_WALK_ITEMS // rp, BAGGED_CHUNK_TREES, n_trees)
+    return min(n, cap) if cap > 0 else n
+
+
+def _pack_bagged_tree(tree, first_leaf_row):
+    """One sklearn ``Tree`` -> (packed nodes, leaf values [leaves][K]),
+    renumbered breadth-first, level by level, so that a node's children are
+    adjacent; leaves number the rows of leaf_values from ``first_leaf_row``
+    in that order."""
+    left, right = tree.children_left, tree.children_right
+    levels, level = [], np.zeros(1, dtype=np.int64)
+    while level.size:
+        levels.append(level)
+        inner = level[left[level] >= 0]
+        level = np.stack([left[inner], right[inner]], axis=1).reshape(-1)
+    order = np.concatenate(levels)
+    n = len(order)
+    assert n == tree.node_count
+    new_of = np.empty(n, dtype=np.int64)
+    new_of[order] = np.arange(n)
+    leaf = left[order] < 0
+    dist = np.where(leaf, 0, new_of[np.where(leaf, 0, left[order])] - np.arange(n))
+    assert np.all(leaf | (new_of[right[order]] == np.arange(n) + dist + 1))
+    assert dist.max(initial=0) < BAGGED_MAX_TREE_NODES
+    missing = getattr(tree, "missing_go_to_left", None)
+    missing_left = np.zeros(n, bool) if missing is None else missing[order].astype(bool)
+    out = np.zeros(n, dtype=BAGGED_NODE_DTYPE)
+    out["thr"] = np.where(leaf, first_leaf_row + np.cumsum(leaf) - 1,
+                          rd32(tree.threshold[order]).view(np.uint32))
+    out["meta"] = (np.where(leaf, 0, tree.feature[order]).astype(np.uint32)
+                   | np.where(~leaf & missing_left, np.uint32(BAGGED_META_MISSING_LEFT),
+                              np.uint32(0))
+                   | (dist.astype(np.uint32) << BAGGED_META_DIST_SHIFT))
+    return out, np.ascontiguousarray(tree.value[order[leaf], 0, :], dtype=np.float64)
+
+
+def _is_bagged(est) -> bool:
+    from sklearn import ensemble, tree
+
+    # ExtraTreeClassifier / ExtraTreeRegressor derive from the DecisionTree classes
+    return isinstance(est, (ensemble.RandomForestClassifier, ensemble.RandomForestRegressor,
+                            ensemble.ExtraTreesClassifier, ensemble.ExtraTreesRegressor,
+                            tree.DecisionTreeClassifier, tree.DecisionTreeRegressor))
+
+
+class BaggedForestPredictor:
+    """A packed random forest, extra-trees ensemble or single decision tree
+    on one device: the mean over the trees of the leaves' fp64 vectors, in
+    sklearn's ``n_jobs=None`` order, bit for bit (docs/kernels.md
+    "Bagged-forest inference"). Build with :meth:`from_sklearn`."""
+
+    def __init__(self, nodes, tree_first, leaf_values, n_features, classes=None, device=None):
+        if device is None:
+            device = "cuda" if torch.cuda.is_available() else "cpu"
+        self.device = torch.device(device)
+        self.n_features = int(n_features)
+        self.n_scores = int(leaf_values.shape[1])
+        self.n_trees = int(len(tree_first) - 1)
+        self.max_tree_nodes = int(np.diff(tree_first).max())
+        self.rows_per_wg = bagged_rows_per_wg(self.n_features, self.n_scores)
+        self.classes_ = None if classes is None else np.asarray(classes)
+        self._nodes_np, self._first_np, self._values_np = nodes, tree_first, leaf_values
+        self._ext = None
+        if self.device.type == "cuda":
+            self._ext = hip_ext(required=True)
+            self._nodes = torch.from_numpy(nodes.view("<i4").reshape(-1, 2)).to(self.device)
+            self._first = torch.from_numpy(tree_first).to(self.device)
+            self._values = torch.from_numpy(leaf_values).to(self.device)
+
+    @classmethod
+    def from_sklearn(cls, est, device=None):
+        if not _is_bagged(est):
+            raise TypeError(f"{type(est).__name__} is no random forest, extra-trees "
+                            "ensemble or decision tree")
+        trees = [e.tree_ for e in getattr(est, "estimators_", [est])]
+        if int(est.n_outputs_) > 1:
+            raise ValueError(f"{est.n_outputs_} outputs: the bagged kernel takes one")
+        classes = getattr(est, "classes_", None)
+        K = 1 if classes is None else len(classes)
+        if not 1 <= K <= MAX_CLASSES:
+            raise ValueError(f"{K} classes: the kernel takes 1..{MAX_CLASSES}")
+        F = int(est.n_features_in_)
+        if F > MAX_FEATURES:
+            raise ValueError(f"{F} features: the row tile takes at most {MAX_FEATURES}")
+        largest = max(t.node_count for t in trees)
+        if largest > BAGGED_MAX_TREE_NODES:
+            raise ValueError(f"a tree has {largest} nodes: a child distance has 20 bits")
+        if sum(t.node_count for t in trees) > 1 << 30:
+            raise ValueError("the forest has more than 2^30 nodes")
+        packed, first_leaf_row = [], 0
+        for t in trees:
+            packed.append(_pack_bagged_tree(t, first_leaf_row))
+            first_leaf_row += len(packed[-1][1])
+        nodes = np.concatenate([p[0] for p in packed])
+        leaf_values = np.concatenate([p[1] for p in packed])
+        tree_first = np.concatenate([[0], np.cumsum([t.node_count for t in trees])])
+        return cls(nodes, tree_first.astype(np.int32), leaf_values, F, classes=classes,
+                   device=device)
+
+    # -- scoring ----------------------------------------------------------------
+
+    def _rows(self, X):
+        if hasattr(X, "tocsr"):
+            raise ValueError("a sparse X is not supported: pass a dense float [B][F]")
+        X = torch.as_tensor(np.asarray(X) if not torch.is_tensor(X) else X)
+        if X.dim() != 2 or X.shape[1] != self.n_features or not X.is_floating_point():
+            raise ValueError(f"X must be a float [B][{self.n_features}], is {tuple(X.shape)} "
+                             f"{X.dtype}")
+        return X.to(self.device, torch.float32).contiguous()
+
+    def _score(self, X, prefix_nodes=-1, trees_per_chunk=0):
+        """-> (means fp64 [B][K], class indices int32 [B]) on the device."""
+        X = self._rows(X)
+        B, K = X.shape[0], self.n_scores
+        probs = torch.empty(B, K, dtype=torch.float64, device=self.device)
+        labels = torch.empty(B, dtype=torch.int32, device=self.device)
+        if B == 0:
+            return probs, labels
+        if self._ext is not None:
+            self._ext.bagged_forest_predict(X, self._nodes, self._first, self._values,
+                                            self.max_tree_nodes, probs, labels,
+                                            prefix_nodes, trees_per_chunk)
+            return probs, labels
+        p = self._walk_cpu(X.numpy())
+        probs.copy_(torch.from_numpy(p))
+        labels.copy_(torch.from_numpy(p.argmax(axis=1).astype(np.int32)))   # first largest
+        return probs, labels
+
+    def _leaves_cpu(self, X, t):
+        """leaf_values rows that the rows of X reach in tree t."""
+        thr_bits, meta = self._nodes_np["thr"], self._nodes_np["meta"]
+        thr = thr_bits.view(np.float32)
+        rows = np.arange(X.shape[0])
+        idx = np.full(X.shape[0], int(self._first_np[t]))
+        while True:
+            m = meta[idx]
+            dist = (m >> BAGGED_META_DIST_SHIFT).astype(np.int64)
+            x = X[rows, m & 0x7FF]
+            with np.errstate(invalid="ignore"):
+                go_left = np.where(np.isnan(x), (m & BAGGED_META_MISSING_LEFT) != 0,
+                                   x <= thr[idx])
+            if not dist.any():
+                return thr_bits[idx].astype(np.int64)
+            idx = idx + np.where(dist > 0, dist + np.where(go_left, 0, 1), 0)
+
+    def _walk_cpu(self, X):
+        """The packed arrays walked on the host, the trees added in order and
+        the sum divided once, as the kernel does -> fp64 [B][K]."""
+        acc = np.zeros((X.shape[0], self.n_scores))
+        for t in range(self.n_trees):
+            acc += self._values_np[self._leaves_cpu(X, t)]
+        acc /= self.n_trees
+        return acc
+
+    def predict_proba(self, X, prefix_nodes=-1, trees_per_chunk=0):
+        """Class probabilities, fp64 ``[B][n_classes]`` on the predictor's
+        device: sklearn's ``predict_proba`` (fitted with ``n_jobs=None``) bit
+        for bit. ``prefix_nodes`` and ``trees_per_chunk`` cap the kernel's
+        LDS prefix and chunk (tests)."""
+        if self.classes_ is None:
+            raise ValueError("predict_proba() needs a classifier")
+        return self._score(X, prefix_nodes, trees_per_chunk)[0]
+
+    def predict(self, X, prefix_nodes=-1, trees_per_chunk=0):
+        """Classifier: ``classes_`` at the first largest probability, a numpy
+        array. Regressor: the values, fp64 ``[B]`` on the device."""
+        probs, labels = self._score(X, prefix_nodes, trees_per_chunk)
+        if self.classes_ is None:
+            return probs[:, 0]
+        return self.classes_[labels.cpu().numpy()]
+
+
+def from_sklearn(est, device=None):
+    """The device predictor of a fitted sklearn tree model: a
+    :class:`ForestPredictor` for ``HistGradientBoosting*``, a
+    :class:`BaggedForestPredictor` for ``RandomForest*``, ``ExtraTrees*``,
+    ``DecisionTree*`` and ``ExtraTree*``."""
+    if hasattr(est, "_predictors"):
+        return ForestPredictor.from_sklearn(est, device=device)
+    if _is_bagged(est):
+        return BaggedForestPredictor.from_sklearn(est, device=device)
+    raise TypeError(f"no device predictor for {type(est).__name__}")

@@ -1,12 +1,13 @@
 // Torch bindings for the CDNA4 tabular hot-path kernels
 // (tabular_kernels.hip, tabular_gen.hip, tabular_eval.hip, tabular_shuffle.hip,
-// forest_predict.hip; launchers and layout constants: tabular_launch.h,
-// tabular_shuffle.h, forest.h). All launches go to the current torch
+// forest_predict.hip, bagged_forest_predict.hip; launchers and layout
+// constants: tabular_launch.h, tabular_shuffle.h, forest.h, bagged_forest.h). All launches go to the current torch
 // stream so they compose with torch.cuda.graphs capture and RCCL work.
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
+#include "bagged_forest.h"
 #include "forest.h"
 #include "tabular_launch.h"
 #include "tabular_shuffle.h"
@@ -698,7 +699,89 @@ void forest_predict(torch::Tensor X, torch::Tensor nodes, torch::Tensor tree_fir
   TORCH_CHECK(rc == 0, "forest_predict: arguments outside the kernel's range");
 }
 
+// ---------------------------------------------------------------------------
+// bagged-forest inference (bagged_forest_predict.hip): mean leaf vectors and
+// labels of a packed random forest / extra-trees / decision tree
+// (bagged_forest.h)
+// ---------------------------------------------------------------------------
+
+void bagged_forest_predict(torch::Tensor X, torch::Tensor nodes, torch::Tensor tree_first,
+                           torch::Tensor leaf_values, int64_t max_tree_nodes,
+                           torch::Tensor probs, torch::Tensor labels,
+                           int64_t prefix_nodes = -1, int64_t trees_per_chunk = 0) {
+  const int64_t B = check_rows(X, torch::kFloat32, "X");
+  const int64_t F = X.size(1);
+  TORCH_CHECK(F <= BAGGED_MAX_FEATURES, "X has ", F, " features, the row tile takes ",
+              BAGGED_MAX_FEATURES);
+  check(nodes, torch::kInt32, "nodes");
+  TORCH_CHECK(nodes.dim() == 2 && nodes.size(1) == 2 && nodes.size(0) >= 1 &&
+                  nodes.size(0) <= (1 << 30),
+              "nodes must be [1 <= N <= 2^30][2] int32 (8-byte nodes), is ", nodes.sizes());
+  check(tree_first, torch::kInt32, "tree_first");
+  const int64_t T = tree_first.numel() - 1;
+  TORCH_CHECK(tree_first.dim() == 1 && T >= 1 && T <= nodes.size(0),
+              "tree_first must be [T + 1], 1 <= T <= the node count ", nodes.size(0),
+              ", is ", tree_first.sizes());
+  check(leaf_values, torch::kFloat64, "leaf_values");
+  TORCH_CHECK(leaf_values.dim() == 2 && leaf_values.size(0) >= 1 &&
+                  leaf_values.size(0) <= nodes.size(0) && leaf_values.size(1) >= 1 &&
+                  leaf_values.size(1) <= BAGGED_MAX_CLASSES,
+              "leaf_values must be [1 <= L <= N][1 <= K <= ", BAGGED_MAX_CLASSES, "], is ",
+              leaf_values.sizes());
+  const int64_t K = leaf_values.size(1);
+  TORCH_CHECK(max_tree_nodes >= 1 && max_tree_nodes <= BAGGED_MAX_TREE_NODES,
+              "max_tree_nodes must be 1..", BAGGED_MAX_TREE_NODES, ", is ", max_tree_nodes);
+  TORCH_CHECK(prefix_nodes >= -1 && prefix_nodes <= INT_MAX,
+              "prefix_nodes must be -1 (as many as fit) or >= 0, is ", prefix_nodes);
+  TORCH_CHECK(trees_per_chunk >= 0 && trees_per_chunk <= INT_MAX,
+              "trees_per_chunk must be 0 (as many as fit) or positive, is ",
+              trees_per_chunk);
+  check(probs, torch::kFloat64, "probs");
+  TORCH_CHECK(probs.dim() == 2 && probs.size(0) >= B && probs.size(1) == K,
+              "probs must be [>= ", B, "][", K, "], is ", probs.sizes());
+  check_n(labels, torch::kInt32, "labels", B);
+  const Span outs[] = {span_of(probs, "probs"), span_of(labels, "labels")};
+  const Span ins[] = {span_of(X, "X"), span_of(nodes, "nodes"),
+                      span_of(tree_first, "tree_first"),
+                      span_of(leaf_values, "leaf_values")};
+  for (const Span& o : outs)
+    for (const Span& i : ins) check_disjoint(i, o);
+  check_disjoint(outs[0], outs[1]);
+  const int rc = launch_bagged_forest_predict(
+      X.data_ptr<float>(), (int)B, (int)F, (int)K,
+      reinterpret_cast<const BaggedNode*>(nodes.data_ptr()), (int)nodes.size(0),
+      tree_first.data_ptr<int>(), (int)T, (int)max_tree_nodes,
+      leaf_values.data_ptr<double>(), (int)leaf_values.size(0), (int)prefix_nodes,
+      (int)trees_per_chunk, probs.data_ptr<double>(), labels.data_ptr<int>(),
+      current_stream());
+  TORCH_CHECK(rc != -2, "bagged_forest_predict: could not raise the dynamic-LDS limit");
+  TORCH_CHECK(rc == 0, "bagged_forest_predict: arguments outside the kernel's range");
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("bagged_forest_predict", &bagged_forest_predict,
+        "probs[b][k] = (the leaf vectors of trees 0, 1, ... added in order) / T (fp64, "
+        "sklearn's bits at n_jobs=None); labels[b] = the first largest k",
+        py::arg("X"), py::arg("nodes"), py::arg("tree_first"), py::arg("leaf_values"),
+        py::arg("max_tree_nodes"), py::arg("probs"), py::arg("labels"),
+        py::arg("prefix_nodes") = -1, py::arg("trees_per_chunk") = 0);
+  m.def("bagged_rows_per_wg",
+        [](int64_t F, int64_t K) { return bagged_rows_per_wg((int)F, (int)K); },
+        "rows per workgroup of bagged_forest_predict (0: F or K out of range)",
+        py::arg("F"), py::arg("K"));
+  m.def("bagged_trees_per_chunk",
+        [](int64_t rows, int64_t T, int64_t cap) {
+          return bagged_trees_per_chunk((int)rows, (int)T, (int)cap);
+        },
+        "trees per chunk of a workgroup of bagged_forest_predict that holds `rows` rows",
+        py::arg("rows"), py::arg("T"), py::arg("cap") = 0);
+  m.attr("BAGGED_MAX_CLASSES") = BAGGED_MAX_CLASSES;
+  m.attr("BAGGED_MAX_FEATURES") = BAGGED_MAX_FEATURES;
+  m.attr("BAGGED_MAX_TREE_NODES") = BAGGED_MAX_TREE_NODES;
+  m.attr("BAGGED_MAX_ROWS") = BAGGED_MAX_ROWS;
+  m.attr("BAGGED_META_DIST_SHIFT") = BAGGED_META_DIST_SHIFT;
+  m.attr("BAGGED_META_MISSING_LEFT") = BAGGED_META_MISSING_LEFT;
+  m.attr("BAGGED_TILE_BYTES") = BAGGED_TILE_BYTES;
   m.def("forest_predict", &forest_predict,
         "scores[b][k] = baseline[k] + the leaves of trees k, K + k, ... in order "
         "(fp64, sklearn's bits); labels[b] = argmax, or score > 0 at K = 1",
