@@ -32,12 +32,45 @@ __device__ __forceinline__ float bf2f(u16 v) {
   return c.f;
 }
 
-__device__ __forceinline__ u16 f2bf(float f) {
+// float -> bf16, round-to-nearest-even.
+//
+// f2bf_soft is the integer form: add 0x7fff plus the kept lsb, take the high
+// half. It is what every target but gfx950 runs, and the reference that
+// f2bf_selftest_kernel holds the hardware form against.
+//
+// On gfx950 f2bf is the float -> __bf16 cast, which compiles to
+// v_cvt_pk_bf16_f32: one instruction where the integer form is three
+// dependent ones. f2bf_pair converts two values and packs them (lo in bits
+// 0..15, hi in 16..31) with ONE such instruction and no separate pack; every
+// site that stores neighbouring bf16 values goes through it. The two forms
+// agree on every input that is not a NaN, denormals included (all 2^32
+// patterns: tests/test_gpu_f2bf_exhaustive.py). They differ on NaNs only: the
+// integer add carries a NaN with a large payload over into an infinity or a
+// signed zero, the instruction returns a quiet NaN. A NaN stays a NaN.
+__device__ __forceinline__ u16 f2bf_soft(float f) {
   union { float f; unsigned u; } c;
   c.f = f;
   unsigned lsb = (c.u >> 16) & 1u;
   c.u += 0x7fffu + lsb;        // round-to-nearest-even
   return (u16)(c.u >> 16);
+}
+
+__device__ __forceinline__ u16 f2bf(float f) {
+#if defined(__gfx950__)
+  return __builtin_bit_cast(u16, (__bf16)f);
+#else
+  return f2bf_soft(f);
+#endif
+}
+
+__device__ __forceinline__ unsigned f2bf_pair(float lo, float hi) {
+#if defined(__gfx950__)
+  typedef __attribute__((ext_vector_type(2))) float f32x2;
+  typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
+  return __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2){lo, hi}, bf16x2));
+#else
+  return (unsigned)f2bf_soft(lo) | ((unsigned)f2bf_soft(hi) << 16);
+#endif
 }
 
 __device__ __forceinline__ float fast_rcp(float x) {

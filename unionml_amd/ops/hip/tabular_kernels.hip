@@ -406,17 +406,71 @@ __device__ __forceinline__ void zero_dl_pad(const Lds& L) {
 
 // four consecutive bf16 of one row-major LDS image row (8-byte aligned: the
 // column is a multiple of 4 and the row strides are multiples of 16 bytes)
-// as ONE 8-byte store, in place of four 2-byte ones
+// as ONE 8-byte store, in place of four 2-byte ones. The four floats are
+// rounded and packed two at a time (f2bf_pair, tabular_common.h); the packed
+// words are returned for a caller that needs the rounded values again.
 typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
-__device__ __forceinline__ void store_bf16x4(u16* p, const u16 (&x)[4]) {
-  *(u32x2*)p = (u32x2){(unsigned)x[0] | ((unsigned)x[1] << 16),
-                       (unsigned)x[2] | ((unsigned)x[3] << 16)};
+__device__ __forceinline__ u32x2 store_bf16x4(u16* p, const float (&x)[4]) {
+  const u32x2 v = {f2bf_pair(x[0], x[1]), f2bf_pair(x[2], x[3])};
+  *(u32x2*)p = v;
+  return v;
+}
+
+// element r (0..3) of what store_bf16x4 returned, as the float it rounds to
+__device__ __forceinline__ float bf16x4_elem(u32x2 v, int r) {
+  const unsigned w = v[r >> 1];
+  return __uint_as_float((r & 1) ? (w & 0xffff0000u) : (w << 16));
 }
 
 struct ChunkAcc {
   f32x4 dW1;        // wave's dW1^T tile: h-tile = wave&1, in-tile = wave>>1
   f32x4 dW2;        // waves 0-1: dW2 tile (h-tile = wave)
 };
+
+// Timing probe PROBE_STAMPS (benchmarks/probe_floor.hip; never defined in the
+// extension): every wave of mlp_step_fused_kernel reads two clocks at the
+// points below, wall_clock64() (100 MHz, one time base for the whole device:
+// compare workgroups with it) and the cycle counter (compare the waves of
+// one workgroup, or two points of one wave, with it). The readings stay in
+// scalar registers until the wave's last store; then lane 0 writes them with
+// plain vector stores into a buffer of the probe's own, never into a slab.
+// A point a wave does not pass stays 0.
+#ifdef PROBE_STAMPS
+enum {
+  ST_ENTRY,       // kernel entry
+  ST_B1,          // behind the first barrier
+  ST_ROWSEG,      // end of the row segment, in front of the second barrier
+  ST_MFMA,        // behind the wave's last MFMA (issued; the result is not waited for)
+  ST_DRAIN,       // behind the vmcnt(0) drain of the slab stores
+  ST_POLL,        // the polling wave: its poll has matched
+  ST_B4,          // behind the fourth barrier
+  ST_LD_FIRST,    // in front of the first load of the 16-slab batch
+  ST_LD_ISSUED,   // behind the batch's last load, nothing waited for
+  ST_LD_ARRIVED,  // the batch has arrived (vmcnt(0))
+  ST_LAST_STORE,  // the wave's last store is issued
+  ST_POINTS
+};
+struct Stamps {
+  unsigned long long wall[ST_POINTS], cyc[ST_POINTS];
+};
+__device__ unsigned long long* probe_stamps;   // [launch][wg][wave][2][ST_POINTS]
+__device__ unsigned probe_stamps_launches;     // launches the buffer holds
+#define STAMP(st, k)                                             \
+  do {                                                           \
+    __builtin_amdgcn_sched_barrier(0);                           \
+    (st).wall[k] = (unsigned long long)wall_clock64();           \
+    (st).cyc[k] = (unsigned long long)__builtin_readcyclecounter(); \
+    __builtin_amdgcn_sched_barrier(0);                           \
+  } while (0)
+#define STAMPS_DECL Stamps st = {};
+#define STAMPS_PARAM , Stamps& st
+#define STAMPS_ARG , st
+#else
+#define STAMP(st, k) do {} while (0)
+#define STAMPS_DECL
+#define STAMPS_PARAM
+#define STAMPS_ARG
+#endif
 
 // one 128-row chunk: fwd + bwd, accumulating weight grads in acc_io. b1/b2
 // point at fp32 biases in LDS, 16-byte aligned, b2 padded to CPAD floats.
@@ -442,7 +496,7 @@ template <bool SINGLE>
 __device__ __forceinline__ void chunk_fwd_bwd(
     const Lds& L, const float* b1, const float* b2,
     const int label, const bool valid, float invBtot, ChunkAcc& acc_io,
-    float& bias_sum) {
+    float& bias_sum STAMPS_PARAM) {
   const int tid = threadIdx.x;
   const int wave = tid >> 6;
   const int l = tid & 63;
@@ -475,9 +529,9 @@ __device__ __forceinline__ void chunk_fwd_bwd(
   __builtin_amdgcn_sched_barrier(0);
 
   // ---- fwd1: H^T = W1T @ B(Xs);  D: h = mt*16+lg*4+r, row = wrow+lr --------
-  // hbits keeps the lane's eight H values: dH below needs exactly these
-  // (same h, same row), so it does not read Hs back
-  u16 hbits[HID / 16][4];
+  // hbits keeps the lane's eight H values as stored: dH below needs exactly
+  // these (same h, same row), so it does not read Hs back
+  u32x2 hbits[HID / 16];
   f32x4 hacc[HID / 16];
   #pragma unroll
   for (int mt = 0; mt < HID / 16; ++mt) {
@@ -489,14 +543,13 @@ __device__ __forceinline__ void chunk_fwd_bwd(
   }
   #pragma unroll
   for (int mt = 0; mt < HID / 16; ++mt) {
+    float hv[4];
     #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      float hv = hacc[mt][r] + b1v[mt][r];
-      hv = hv > 0.f ? hv : 0.f;
-      const u16 hb = f2bf(hv);
-      hbits[mt][r] = hb;
+      hv[r] = hacc[mt][r] + b1v[mt][r];
+      hv[r] = hv[r] > 0.f ? hv[r] : 0.f;
     }
-    store_bf16x4(&L.Hs[wrow + lr][mt * 16 + lg * 4], hbits[mt]);
+    hbits[mt] = store_bf16x4(&L.Hs[wrow + lr][mt * 16 + lg * 4], hv);
   }
   // NO __syncthreads here: fwd2 reads only THIS wave's rows of Hs
   // (row = wrow+lr), written by lanes of the same wave — a wave-level
@@ -521,17 +574,14 @@ __device__ __forceinline__ void chunk_fwd_bwd(
     const float logs = __logf(s);
     float db2_acc[4];
     float loss_acc = 0.f;
-    u16 dlbits[4];
     #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int c = lg * 4 + r;
       const float dl = valid ? (e[0][r] * rs - (c == label ? 1.f : 0.f)) * invBtot : 0.f;
-      const u16 dlb = f2bf(dl);
-      dlbits[r] = dlb;
       db2_acc[r] = dl;
       if (valid && c == label) loss_acc = -(logit[0][r] - m - logs) * invBtot;
     }
-    store_bf16x4(&L.DLs[row][lg * 4], dlbits);
+    store_bf16x4(&L.DLs[row][lg * 4], db2_acc);
     // reduce db2/loss over the 16 row-lanes (lr bits) first, then ONE
     // plain store per (wave, class) into this wave's partial row: the
     // waves are summed in fixed order below, so the step is reproducible
@@ -565,16 +615,13 @@ __device__ __forceinline__ void chunk_fwd_bwd(
       const bf16x8 a = *(const bf16x8*)&L.W2s[mt * 16 + lr][lg * 8];
       const bf16x8 b = *(const bf16x8*)&L.DLs[wrow + lr][lg * 8];
       acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc, 0, 0, 0);
-      u16 dhbits[4];
       #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const float hv = bf2f(hbits[mt][r]);   // == L.Hs[row][h], this lane's own store
-        const float dh = hv > 0.f ? acc[r] : 0.f;
-        dhbits[r] = f2bf(dh);
-        db1_acc[mt][r] = dh;
+        const float hv = bf16x4_elem(hbits[mt], r);   // == L.Hs[row][h], this lane's own store
+        db1_acc[mt][r] = hv > 0.f ? acc[r] : 0.f;
       }
       // row-major, the lane's four consecutive h of its row as one store
-      store_bf16x4(&L.DHs[wrow + lr][mt * 16 + lg * 4], dhbits);
+      store_bf16x4(&L.DHs[wrow + lr][mt * 16 + lg * 4], db1_acc[mt]);
     }
     // db1[h]: sum this row-block's contribution across the 16 lr lanes.
     // All eight reductions first, no branch between them, then the
@@ -596,6 +643,7 @@ __device__ __forceinline__ void chunk_fwd_bwd(
   }
   // DHs + per-wave partials complete; and every wave's Hs and DLs rows, which
   // dW2 reads across waves
+  STAMP(st, ST_ROWSEG);
   __syncthreads();
 
   // ---- db1/db2/loss += partials, waves in fixed order. The last wave does
@@ -656,6 +704,7 @@ __device__ __forceinline__ void chunk_fwd_bwd(
     }
     acc_io.dW2 = acc;
   }
+  STAMP(st, ST_MFMA);
   // chunk arrays free for reuse: Xs above all, which dW1 has just read and
   // the caller's next store_x_chunk refills
   if constexpr (!SINGLE) __syncthreads();
@@ -699,7 +748,9 @@ mlp_step_kernel(const u16* __restrict__ Xbf, const int* __restrict__ y, int B,
   acc.dW1 = (f32x4){0.f, 0.f, 0.f, 0.f};
   acc.dW2 = (f32x4){0.f, 0.f, 0.f, 0.f};
   float bias_sum;
-  chunk_fwd_bwd<true>(L, L.b1s, L.b2s, chunk_label(xr), xr.valid, invBtot, acc, bias_sum);
+  STAMPS_DECL
+  chunk_fwd_bwd<true>(L, L.b1s, L.b2s, chunk_label(xr), xr.valid, invBtot, acc,
+                      bias_sum STAMPS_ARG);
 
   {
     const int ht = wave & 1, it = wave >> 1;
@@ -812,6 +863,8 @@ mlp_step_fused_kernel(// the seven arguments the prologue's vector loads need
   // vector loads, so that their round trip runs beside those. ---------------
   asm volatile("" :: "s"(Xbf), "s"(y), "s"(B), "s"(wimg), "s"(master), "s"(counter),
                "s"(t_dev));
+  STAMPS_DECL
+  STAMP(st, ST_ENTRY);
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const Lds L = carve(smem);
@@ -873,6 +926,7 @@ mlp_step_fused_kernel(// the seven arguments the prologue's vector loads need
   const unsigned epoch = counter_pre + 1u;
   asm volatile("" :: "v"(epoch), "v"(t_pre));
   __syncthreads();
+  STAMP(st, ST_B1);
 
   ChunkAcc acc;
   acc.dW1 = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -886,7 +940,8 @@ mlp_step_fused_kernel(// the seven arguments the prologue's vector loads need
   // its second-to-last or last GEMM: the publish barrier is behind every
   // wave's dW1, so the prefetch cannot overwrite rows a slower wave still
   // has to read.
-  chunk_fwd_bwd<true>(L, L.b1s, L.b2s, chunk_label(xr), xr.valid, invBtot, acc, bias_sum);
+  chunk_fwd_bwd<true>(L, L.b1s, L.b2s, chunk_label(xr), xr.valid, invBtot, acc,
+                      bias_sum STAMPS_ARG);
 #endif
 
   // ---- write this WG's complete partial slab: write-through (sc1) stores,
@@ -940,6 +995,7 @@ mlp_step_fused_kernel(// the seven arguments the prologue's vector loads need
   // signal for the whole workgroup. No release fence: nothing of the slab is
   // left dirty in L2 for one to write back.
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  STAMP(st, ST_DRAIN);
   __syncthreads();
   if (tid == 0) xwg_store((unsigned*)(slab + NPARAM + 1), epoch);   // (3)
   // No barrier between the tag store and the polls: nothing reads what the
@@ -1027,6 +1083,7 @@ mlp_step_fused_kernel(// the seven arguments the prologue's vector loads need
       }
     }
 #endif
+    STAMP(st, ST_POLL);
     const unsigned long long bad = __ballot(!ok);
     // No agent acquire: every slab load below is an sc1 load, which does
     // not look into this CU's L1, so there is no stale line to invalidate
@@ -1038,6 +1095,7 @@ mlp_step_fused_kernel(// the seven arguments the prologue's vector loads need
   // the polling wave joins this barrier only after its poll has matched:
   // the other waves' slab loads all sit behind it
   __syncthreads();
+  STAMP(st, ST_B4);
   if (lossu[1] != 0u) {             // timed out: poison the loss, keep going
     if (tid == 0 && blockIdx.x == 0) *loss_out = __builtin_nanf("");
     return;
@@ -1077,8 +1135,14 @@ mlp_step_fused_kernel(// the seven arguments the prologue's vector loads need
     int w = 0;
     for (; w + 16 <= n_wg; w += 16) {
       float a[16];
+      STAMP(st, ST_LD_FIRST);
       #pragma unroll
       for (int k = 0; k < 16; ++k) a[k] = xwg_load(&slabs[(long long)(w + k) * SLAB + i]);
+      STAMP(st, ST_LD_ISSUED);
+#ifdef PROBE_STAMPS
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      STAMP(st, ST_LD_ARRIVED);
+#endif
       #pragma unroll
       for (int k = 0; k < 16; ++k) gc[k & 7] += a[k];
     }
@@ -1127,6 +1191,18 @@ mlp_step_fused_kernel(// the seven arguments the prologue's vector loads need
     *counter = epoch;
     if (!grads_out) *t_dev = (int)t_new;
   }
+#ifdef PROBE_STAMPS
+  STAMP(st, ST_LAST_STORE);
+  if (l == 0 && counter_pre < probe_stamps_launches) {
+    unsigned long long* rec =
+        probe_stamps + (((size_t)counter_pre * n_wg + blockIdx.x) * WAVES + wave) * 2 * ST_POINTS;
+    #pragma unroll
+    for (int k = 0; k < ST_POINTS; ++k) {
+      rec[k] = st.wall[k];
+      rec[ST_POINTS + k] = st.cyc[k];
+    }
+  }
+#endif
 }
 
 // ---------------------------------------------------------------------------
@@ -1265,8 +1341,9 @@ mlp_train_steps_kernel(const u16* __restrict__ Xbf,  // [N][IN] staged bf16
       store_x_chunk(xr, L);
       __syncthreads();
       float unused;
+      STAMPS_DECL
       chunk_fwd_bwd<false>(L, master_s + OFF_B1, master_s + OFF_B2, chunk_label(xr),
-                           xr.valid, invB, acc, unused);
+                           xr.valid, invB, acc, unused STAMPS_ARG);
     }
 
     // ---- fused in-LDS Adam --------------------------------------------------
@@ -1434,6 +1511,47 @@ reduce_selftest_kernel(const float* __restrict__ x, int n,
 }
 
 // ---------------------------------------------------------------------------
+// f2bf self-test: every one of the 2^32 float bit patterns goes through the
+// target's f2bf and through both halves of f2bf_pair, and through the integer
+// form f2bf_soft (tabular_common.h). One launch, grid-stride. counts[0]: inputs
+// that are no NaN and on which any of the three differs from the integer form;
+// counts[1]: NaN inputs for which any of the three is not a NaN; up to
+// F2BF_SELFTEST_EXAMPLES differing inputs land in examples (counts[2] says
+// how many), in arrival order.
+// ---------------------------------------------------------------------------
+
+extern "C" __global__ void __launch_bounds__(256)
+f2bf_selftest_kernel(unsigned long long* __restrict__ counts,
+                     unsigned* __restrict__ examples) {
+  const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
+  unsigned long long diff = 0, nan_lost = 0;
+  for (unsigned long long n = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+       n < (1ull << 32); n += stride) {
+    const unsigned u = (unsigned)n;
+    const float f = __uint_as_float(u);
+    // the pair's other half takes the pattern with the sign flipped, so both
+    // halves see all 2^32 patterns over the launch
+    const unsigned pair = f2bf_pair(f, __uint_as_float(u ^ 0x80000000u));
+    const u16 got[3] = {f2bf(f), (u16)(pair & 0xffffu), (u16)((pair >> 16) ^ 0x8000u)};
+    const u16 want = f2bf_soft(f);
+    const bool in_nan = (u & 0x7fffffffu) > 0x7f800000u;
+    bool bad = false;
+    #pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      bad |= in_nan ? (got[k] & 0x7fffu) <= 0x7f80u : got[k] != want;
+    }
+    if (bad && in_nan) ++nan_lost;
+    if (bad && !in_nan) {
+      ++diff;
+      const unsigned long long slot = atomicAdd(&counts[2], 1ull);
+      if (slot < F2BF_SELFTEST_EXAMPLES) examples[slot] = u;
+    }
+  }
+  if (diff) atomicAdd(&counts[0], diff);
+  if (nan_lost) atomicAdd(&counts[1], nan_lost);
+}
+
+// ---------------------------------------------------------------------------
 // host launchers (extern "C"; stream-ordered, capture-safe)
 // ---------------------------------------------------------------------------
 
@@ -1545,6 +1663,13 @@ void launch_reduce_selftest(const float* x, int n, float* out,
   if (n <= 0) return;
   hipLaunchKernelGGL(reduce_selftest_kernel, dim3(n), dim3(64), 0, stream, x, n,
                      out);
+}
+
+void launch_f2bf_selftest(unsigned long long* counts, unsigned* examples,
+                          hipStream_t stream) {
+  // 2048 workgroups of 256: 8192 patterns per thread
+  hipLaunchKernelGGL(f2bf_selftest_kernel, dim3(2048), dim3(256), 0, stream, counts,
+                     examples);
 }
 
 }  // extern "C"

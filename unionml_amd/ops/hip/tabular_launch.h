@@ -201,6 +201,13 @@ void launch_adam_step(float* master, unsigned short* bfmirror, const float* grad
 // by the kernels' DPP helper, and by the plain shuffle butterfly
 void launch_reduce_selftest(const float* x, int n, float* out,
                             hipStream_t stream);
+// all 2^32 float bit patterns through f2bf / f2bf_pair (the target's form)
+// and through f2bf_soft. counts [3], zeroed by the caller: non-NaN inputs
+// whose results differ, NaN inputs whose result is not a NaN, and the
+// examples taken; examples [F2BF_SELFTEST_EXAMPLES] receives differing inputs
+constexpr int F2BF_SELFTEST_EXAMPLES = 16;
+void launch_f2bf_selftest(unsigned long long* counts, unsigned* examples,
+                          hipStream_t stream);
 
 // ---- tabular_gen.hip (any geometry) -----------------------------------------
 

@@ -340,6 +340,23 @@ torch::Tensor reduce_selftest(torch::Tensor x) {
   return out;
 }
 
+// (non-NaN inputs on which the target's bf16 rounding differs from the integer
+// form, up to F2BF_SELFTEST_EXAMPLES of them in ascending order, NaN inputs
+// whose result is no NaN), over all 2^32 bit patterns, on the current device
+std::tuple<int64_t, torch::Tensor, int64_t> f2bf_selftest() {
+  const auto dev = torch::TensorOptions().device(torch::kCUDA);
+  torch::Tensor counts = torch::zeros({3}, dev.dtype(torch::kInt64));
+  torch::Tensor examples = torch::zeros({F2BF_SELFTEST_EXAMPLES}, dev.dtype(torch::kInt32));
+  launch_f2bf_selftest(reinterpret_cast<unsigned long long*>(counts.data_ptr<int64_t>()),
+                       reinterpret_cast<unsigned*>(examples.data_ptr<int>()),
+                       current_stream());
+  const torch::Tensor c = counts.cpu();
+  const int64_t taken = std::min<int64_t>(c[2].item<int64_t>(), F2BF_SELFTEST_EXAMPLES);
+  // as unsigned bit patterns, in ascending order
+  torch::Tensor ex = examples.cpu().slice(0, 0, taken).to(torch::kInt64).bitwise_and(0xffffffffLL);
+  return {c[0].item<int64_t>(), std::get<0>(ex.sort()), c[1].item<int64_t>()};
+}
+
 // ---------------------------------------------------------------------------
 // generalized-geometry (any in_features/hidden/classes) entry points
 // ---------------------------------------------------------------------------
@@ -860,6 +877,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "x [n][64] -> [n][64][2]: in-row sums of 16 by the DPP helper and by "
         "the shuffle butterfly (must be bit-equal)",
         py::arg("x"));
+  m.def("f2bf_selftest", &f2bf_selftest,
+        "all 2^32 float bit patterns through the target's float -> bf16 "
+        "rounding and through the integer form: (non-NaN inputs that differ, "
+        "the first few of them, NaN inputs whose result is no NaN)");
   m.def("mlp_step_gen", &mlp_step_gen,
         "generalized fused step: any (in,hid,cls) geometry; double-buffered "
         "K-tiled MFMA fwd+bwd producing per-WG gradient slabs",
