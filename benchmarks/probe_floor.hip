@@ -18,7 +18,7 @@
 //                        counts of this build, not its time)
 // And one for where the waves stand inside the step:
 //   -DPROBE_STAMPS       every wave records the wall clock and the cycle
-//                        counter at eleven points (ST_* in the kernel file)
+//                        counter at fourteen points (ST_* in the kernel file)
 //                        into a buffer of the probe's; the probe prints which
 //                        wave is last at the second and at the third barrier,
 //                        how often and by how much, and the span of the
@@ -40,7 +40,8 @@
 
 static const char* const ST_NAMES[ST_POINTS] = {
     "entry", "behind b1", "row seg end", "last MFMA", "store drain", "poll matched",
-    "behind b4", "first slab load", "loads issued", "loads arrived", "last store"};
+    "behind b4", "first slab load", "loads issued", "loads arrived", "verdict read",
+    "g folded", "p computed", "last store"};
 
 // which wave of a workgroup reaches `point` last (cycle counter: one CU), how
 // often, and its mean lead over the second-to-last wave

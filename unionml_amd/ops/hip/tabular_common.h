@@ -300,15 +300,26 @@ __device__ __forceinline__ void adam_bias_corr(float beta1, float beta2, float t
 // subtraction, hence a single way to contract it. The statements keep the
 // evaluation order of the plain expression they replace, so the three
 // fused kernels compile to the instructions they had before.
-__device__ __forceinline__ void adam_update(float& p, float& m, float& v, float g,
-                                            float lr, float beta1, float beta2,
-                                            float eps, float corr1, float corr2) {
+//
+// Two halves: adam_decay needs no gradient (bm = rn(beta1*m), bv =
+// rn(beta2*v)), adam_apply takes the gradient and the two decayed moments.
+// A caller that holds m and v before its gradient exists (the fused step's
+// stripe lanes) calls them apart; adam_update is the two in a row.
+__device__ __forceinline__ void adam_decay(float m, float v, float beta1, float beta2,
+                                           float& bm, float& bv) {
+  #pragma clang fp contract(off)
+  bm = beta1 * m;
+  bv = beta2 * v;
+}
+
+__device__ __forceinline__ void adam_apply(float& p, float& m, float& v, float g,
+                                           float bm, float bv, float lr, float beta1,
+                                           float beta2, float eps, float corr1,
+                                           float corr2) {
   const float omb1 = 1.f - beta1, omb2 = 1.f - beta2;
-  float bm, bv, gs;
+  float gs;
   {
     #pragma clang fp contract(off)
-    bm = beta1 * m;
-    bv = beta2 * v;
     gs = omb2 * g;
   }
   const float mi = __builtin_fmaf(omb1, g, bm);
@@ -318,26 +329,47 @@ __device__ __forceinline__ void adam_update(float& p, float& m, float& v, float 
   p = p - lr * (mi * corr1) * fast_rcp(sqrtf(vi * corr2) + eps);
 }
 
+__device__ __forceinline__ void adam_update(float& p, float& m, float& v, float g,
+                                            float lr, float beta1, float beta2,
+                                            float eps, float corr1, float corr2) {
+  float bm, bv;
+  adam_decay(m, v, beta1, beta2, bm, bv);
+  adam_apply(p, m, v, g, bm, bv, lr, beta1, beta2, eps, corr1, corr2);
+}
+
 // ---------------------------------------------------------------------------
 // packed weight images: Adam-phase maintenance, flat param index i -> the
 // image element(s) that mirror it (biases have none)
 // ---------------------------------------------------------------------------
 
 // specialized layout: the three LDS images incl. their K-pads
-// (tabular_launch.h DIGITS_WIMG_*)
-__device__ __forceinline__ void wimg_write(u16* __restrict__ wimg, int i, u16 wb) {
+// (tabular_launch.h DIGITS_WIMG_*). wimg_targets: how many image elements
+// mirror parameter i (0 for a bias, 1 for W1, 2 for W2) and which (t0, t1).
+__device__ __forceinline__ int wimg_targets(int i, int& t0, int& t1) {
   static_assert(DIGITS_HID == 32 && DIGITS_CPAD == 16, "shifts below");
+  t0 = t1 = 0;
   if (i < DIGITS_OFF_B1) {                              // W1: i = in*HID + h
     const int in = i >> 5;                              // /HID
     const int h = i & 31;
-    wimg[DIGITS_WIMG_W1T + h * DIGITS_XS + in] = wb;
-  } else if (i >= DIGITS_OFF_W2 && i < DIGITS_OFF_B2) { // W2: j = h*CPAD + c
+    t0 = DIGITS_WIMG_W1T + h * DIGITS_XS + in;
+    return 1;
+  }
+  if (i >= DIGITS_OFF_W2 && i < DIGITS_OFF_B2) {        // W2: j = h*CPAD + c
     const int j = i - DIGITS_OFF_W2;
     const int h = j >> 4;                               // /CPAD
     const int c = j & 15;
-    wimg[DIGITS_WIMG_W2S + h * DIGITS_WS + c] = wb;
-    wimg[DIGITS_WIMG_W2T + c * DIGITS_WS + h] = wb;
+    t0 = DIGITS_WIMG_W2S + h * DIGITS_WS + c;
+    t1 = DIGITS_WIMG_W2T + c * DIGITS_WS + h;
+    return 2;
   }
+  return 0;
+}
+
+__device__ __forceinline__ void wimg_write(u16* __restrict__ wimg, int i, u16 wb) {
+  int t0, t1;
+  const int n = wimg_targets(i, t0, t1);
+  if (n >= 1) wimg[t0] = wb;
+  if (n == 2) wimg[t1] = wb;
 }
 
 // generalized layout (bf16 elems): W1T [hid][inp], then W2s [hid][32]

@@ -447,6 +447,9 @@ enum {
   ST_LD_FIRST,    // in front of the first load of the 16-slab batch
   ST_LD_ISSUED,   // behind the batch's last load, nothing waited for
   ST_LD_ARRIVED,  // the batch has arrived (vmcnt(0))
+  ST_VERDICT,     // the poll's verdict word has been read from LDS
+  ST_FOLD,        // the stripe sum g is folded
+  ST_ADAM,        // the new parameter p is computed (the Adam arithmetic has ended)
   ST_LAST_STORE,  // the wave's last store is issued
   ST_POINTS
 };
@@ -829,6 +832,38 @@ constexpr int STRIPE_T0 = 64;
 constexpr int STRIPE_STEP = BLOCK - STRIPE_T0;
 __device__ __forceinline__ int stripe_first(int lo, int tid) { return lo + (tid - STRIPE_T0); }
 
+// The stripe sum of word i from slab w on, for the batches behind the first
+// one and for second and later passes: 16 slabs at a time, then 8, then the
+// remainder's up to 7 in one batch as well.
+__device__ __forceinline__ void stripe_sum_from(float (&gc)[8], const float* slabs, int i,
+                                                int w, int n_wg) {
+  for (; w + 16 <= n_wg; w += 16) {
+    float a[16];
+    #pragma unroll
+    for (int k = 0; k < 16; ++k) a[k] = xwg_load(&slabs[(long long)(w + k) * SLAB + i]);
+    #pragma unroll
+    for (int k = 0; k < 16; ++k) gc[k & 7] += a[k];
+  }
+  for (; w + 8 <= n_wg; w += 8) {
+    float a[8];
+    #pragma unroll
+    for (int k = 0; k < 8; ++k) a[k] = xwg_load(&slabs[(long long)(w + k) * SLAB + i]);
+    #pragma unroll
+    for (int k = 0; k < 8; ++k) gc[k] += a[k];
+  }
+  if (w < n_wg) {
+    float a[7];
+    #pragma unroll
+    for (int k = 0; k < 7; ++k) {
+      a[k] = xwg_load(&slabs[(long long)min(w + k, n_wg - 1) * SLAB + i]);
+    }
+    #pragma unroll
+    for (int k = 0; k < 7; ++k) {
+      if (w + k < n_wg) gc[0] += a[k];
+    }
+  }
+}
+
 extern "C" __global__ void __launch_bounds__(BLOCK)
 mlp_step_fused_kernel(// the seven arguments the prologue's vector loads need
                       // come first: 14 dwords, inside the 16 that the build's
@@ -982,12 +1017,22 @@ mlp_step_fused_kernel(// the seven arguments the prologue's vector loads need
   // the chunk arrays are dead behind the publish barrier (every wave's dW1
   // reads of Xs are done there) — reuse Xs
   float* pre = (float*)L.Xs;
-  const int span_pre = (NPARAM + 1 + n_wg - 1) / n_wg;
-  const int lo_pre = blockIdx.x * span_pre;
+  const int span = (NPARAM + 1 + n_wg - 1) / n_wg;
+  const int lo = blockIdx.x * span;
+  const int hi = min(lo + span, NPARAM + 1);
   const bool use_pre =
-      (grads_out == nullptr) && (3 * span_pre * 4 <= ROWS * XS * 2);
+      (grads_out == nullptr) && (3 * span * 4 <= ROWS * XS * 2);
   const float t_new = (float)(t_pre + 1u);
   float corr1 = 0.f, corr2 = 0.f;   // Adam bias corrections (fused mode only)
+  // A stripe lane's first pass, prepared in the poll window (below): the
+  // parameter i0, the addresses of the first batch of slab loads, the Adam
+  // state and its decayed moments, the image targets.
+  const int i0 = stripe_first(lo, tid);
+  const bool active = wave != 0 && i0 < hi;
+  const bool adam0 = active && !grads_out && i0 < NPARAM;
+  const float* A[16];
+  float p0 = 0.f, m0 = 0.f, v0 = 0.f, bm0 = 0.f, bv0 = 0.f;
+  int nimg = 0, t0 = 0, t1 = 0;
 #ifndef PROBE_SKIP_HANDSHAKE
   // Condition (2): EVERY storing wave waits until its write-through stores
   // have completed (inline asm, so no compiler pass can drop the wait), and
@@ -1002,34 +1047,37 @@ mlp_step_fused_kernel(// the seven arguments the prologue's vector loads need
   // tag store orders. Lane 0 sits in the polling wave itself, the other
   // waves only work on their own Adam stripe until the barrier behind the
   // poll, and another workgroup sees the tag whenever it arrives.
-
+  //
   // Two roles until that barrier. Wave 0 is the hand-off wave and nothing
   // else: from the tag store it goes straight to its first poll, with no
-  // load of its own to wait for. Waves 1 to 7 do two things WHILE the sweep
-  // waits. They prefetch this WG's Adam-state stripe (master/m/v) into LDS —
-  // these are only ever written by this same WG's stripe in the reduce
-  // phase, so plain loads ahead of the poll are safe (condition (4)), and it
-  // pulls an HBM round trip out of the reduce chain. And two of them compute
-  // the Adam bias corrections, two full pow expansions whose only inputs
-  // (beta1, beta2, t_pre) every thread has held since the prologue: wave 1
-  // corr1, wave 2 corr2, one chain each, so that the pair takes the time of
-  // one (both chains in every stripe wave outlast the poll and hold the
-  // barrier up). The stripe's first loads go out, the arithmetic runs while
-  // they are in flight, and the empty asm pins it here (left alone the
-  // compiler sinks the pure arithmetic to its use, behind the last barrier
-  // and in front of the first slab load). The values cross the barrier in
-  // L.loss[2] and [3]. Reduce-only launches need no correction and compute
-  // none.
+  // load of its own to wait for.
+#endif
   if (wave != 0) {
-    const int hi_pre = min(lo_pre + span_pre, NPARAM);
-    int i = stripe_first(lo_pre, tid);
-    const bool first = use_pre && i < hi_pre;
-    float p0 = 0.f, m0 = 0.f, v0 = 0.f;
-    if (first) {
-      p0 = master[i];
-      m0 = m[i];
-      v0 = v[i];
+    // Waves 1 to 7 do three things WHILE the sweep waits. They prefetch the
+    // first pass of this WG's Adam-state stripe (master/m/v) into registers
+    // and the later passes into LDS: these are only ever written by this
+    // same WG's stripe in the reduce phase, so plain loads ahead of the poll
+    // are safe (condition (4)), and it pulls an HBM round trip out of the
+    // reduce chain. Two of them compute the Adam bias corrections, two full
+    // pow expansions whose only inputs (beta1, beta2, t_pre) every thread
+    // has held since the prologue: wave 1 corr1, wave 2 corr2, one chain
+    // each, so that the pair takes the time of one (both chains in every
+    // stripe wave outlast the poll and hold the barrier up). And all of them
+    // compute whatever the tail behind the barrier needs that no slab word
+    // enters: the 64-bit addresses of the first batch of slab loads (the
+    // loads only go out behind the barrier), the image targets, and the
+    // products rn(beta1*m), rn(beta2*v) of adam_update. The stripe's first
+    // loads go out, the arithmetic runs while they are in flight, and the
+    // empty asm statements pin it here (left alone the compiler sinks pure
+    // arithmetic to its use, behind the last barrier and in front of the
+    // first slab load). The corrections cross the barrier in L.loss[2] and
+    // [3]. Reduce-only launches need no correction and compute none.
+    if (adam0) {
+      p0 = master[i0];
+      m0 = m[i0];
+      v0 = v[i0];
     }
+#ifndef PROBE_SKIP_HANDSHAKE
     if (!grads_out && wave <= 2) {
 #ifdef PROBE_CONST_CORR
       const float c = wave == 1 ? 10.f : 1000.f;   // timing probe: no pow
@@ -1039,21 +1087,44 @@ mlp_step_fused_kernel(// the seven arguments the prologue's vector loads need
       asm volatile("" :: "v"(c));
       if (l == 0) L.loss[1 + wave] = c;
     }
-    if (first) {
-      const int j = i - lo_pre;
-      pre[j] = p0;
-      pre[span_pre + j] = m0;
-      pre[2 * span_pre + j] = v0;
+#endif
+    // load k of the first batch reads slab k, clamped into the grid (a
+    // clamped load is issued only where its add is predicated off); a grid
+    // below 8 issues seven loads and computes seven addresses
+    #pragma unroll
+    for (int k = 0; k < 7; ++k) {
+      A[k] = slabs + (long long)min(k, n_wg - 1) * SLAB + i0;
+      asm volatile("" :: "v"(A[k]));
     }
-    if (use_pre) {
-      for (i += STRIPE_STEP; i < hi_pre; i += STRIPE_STEP) {
-        const int j = i - lo_pre;
-        pre[j] = master[i];
-        pre[span_pre + j] = m[i];
-        pre[2 * span_pre + j] = v[i];
+    if (n_wg >= 8) {
+      #pragma unroll
+      for (int k = 7; k < 16; ++k) {
+        A[k] = slabs + (long long)min(k, n_wg - 1) * SLAB + i0;
+        asm volatile("" :: "v"(A[k]));
       }
     }
-  } else {
+    if (wimg && adam0) nimg = wimg_targets(i0, t0, t1);
+    asm volatile("" :: "v"(nimg), "v"(t0), "v"(t1));
+    if (use_pre) {
+      const int hi_pre = min(hi, NPARAM);
+      for (int i = i0 + STRIPE_STEP; i < hi_pre; i += STRIPE_STEP) {
+        const int j = i - lo;
+        pre[j] = master[i];
+        pre[span + j] = m[i];
+        pre[2 * span + j] = v[i];
+      }
+    }
+    // one opaque statement per value: paired up, the two products would
+    // become one packed multiply of a form no other kernel here uses
+    asm volatile("" : "+v"(m0));
+    asm volatile("" : "+v"(v0));
+    adam_decay(m0, v0, beta1, beta2, bm0, bv0);
+    asm volatile("" : "+v"(bm0));
+    asm volatile("" : "+v"(bv0));
+    asm volatile("" :: "v"(p0));
+  }
+#ifndef PROBE_SKIP_HANDSHAKE
+  else {
     // relaxed PARALLEL sweep: lane j polls tags j, j+64, ... (G16: never
     // poll with an acquire). One vector gather per poll round — one
     // memory round trip after the last publish, independent of n_wg
@@ -1096,10 +1167,6 @@ mlp_step_fused_kernel(// the seven arguments the prologue's vector loads need
   // the other waves' slab loads all sit behind it
   __syncthreads();
   STAMP(st, ST_B4);
-  if (lossu[1] != 0u) {             // timed out: poison the loss, keep going
-    if (tid == 0 && blockIdx.x == 0) *loss_out = __builtin_nanf("");
-    return;
-  }
 #endif  // PROBE_SKIP_HANDSHAKE
 
 #ifdef PROBE_SKIP_REDUCE
@@ -1110,82 +1177,139 @@ mlp_step_fused_kernel(// the seven arguments the prologue's vector loads need
   return;
 #endif
   // ---- every WG reduces its own param stripe + applies Adam ----------------
+  // Eight chains: chain k sums the slabs w = k, k+8, k+16, ... in that
+  // order; the remainder (n_wg % 8 slabs) goes into chain 0; then the
+  // chains are folded pairwise. That order is pinned bit for bit. What is
+  // free is how many loads are in flight and which lane adds what. Each
+  // batch issues ALL its loads before its first add (a batch is one memory
+  // round trip, and a written-through slab word is in no L2). A clamped
+  // load reads the grid's last slab once more and only the ADD is
+  // predicated (adding a zero instead could turn a -0 sum into +0). Every
+  // slab word through xwg_load (sc1, past the L1): condition (4).
+  //
+  // The first batch of the first pass is the first thing behind the barrier:
+  // its addresses are in registers, and the verdict word and the corrections
+  // are read from LDS while it is in flight. It covers the first 16 slabs:
+  // two groups of eight, or one group and the remainder, or the remainder
+  // alone. A timed-out launch has issued these loads (they read valid slab
+  // memory) and returns before any store.
+  // the chains' zeros, opaque: with a literal 0 the first adds of two chains
+  // become one packed add of a form no other kernel here uses
+  float z0 = 0.f, z1 = 0.f;
+  asm volatile("" : "+v"(z0));
+  asm volatile("" : "+v"(z1));
+  const int n_first = n_wg >= 16 ? 16 : n_wg >= 8 ? 15 : 7;
+  unsigned verdict = 0u;
 #ifdef PROBE_SKIP_HANDSHAKE
   // timing probe without the hand-off window: the corrections at their use
   if (!grads_out) adam_bias_corr(beta1, beta2, t_new, corr1, corr2);
-#else
-  if (!grads_out) corr1 = L.loss[2], corr2 = L.loss[3];
 #endif
-  const int span = (NPARAM + 1 + n_wg - 1) / n_wg;
-  const int lo = blockIdx.x * span;
-  const int hi = min(lo + span, NPARAM + 1);
-  for (int i = stripe_first(lo, tid); wave != 0 && i < hi; i += STRIPE_STEP) {
-    // Eight chains: chain k sums the slabs w = k, k+8, k+16, ... in that
-    // order; the remainder (n_wg % 8 slabs) goes into chain 0; then the
-    // chains are folded pairwise. That order is pinned bit for bit. What is
-    // free is how many loads are in flight: each batch below issues ALL its
-    // loads before its first add (a batch is one memory round trip, and a
-    // written-through slab word is in no L2), 16 slabs at a time, then 8,
-    // then the remainder's up to 7 in one batch as well. The remainder
-    // loads unconditionally, past the grid's end the last slab once more,
-    // and only the ADD is predicated (adding a zero instead could turn a
-    // -0 sum into +0). Every slab word through xwg_load (sc1, past the
-    // L1): condition (4).
-    float gc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    int w = 0;
-    for (; w + 16 <= n_wg; w += 16) {
-      float a[16];
-      STAMP(st, ST_LD_FIRST);
+  if (!active) {
+#ifndef PROBE_SKIP_HANDSHAKE
+    verdict = lossu[1];
+#endif
+  } else {
+    float a[16];
+    STAMP(st, ST_LD_FIRST);
+    #pragma unroll
+    for (int k = 0; k < 7; ++k) a[k] = xwg_load(A[k]);
+    if (n_first >= 15) {
       #pragma unroll
-      for (int k = 0; k < 16; ++k) a[k] = xwg_load(&slabs[(long long)(w + k) * SLAB + i]);
-      STAMP(st, ST_LD_ISSUED);
+      for (int k = 7; k < 15; ++k) a[k] = xwg_load(A[k]);
+      if (n_first >= 16) a[15] = xwg_load(A[15]);
+    }
+    STAMP(st, ST_LD_ISSUED);
+#ifndef PROBE_SKIP_HANDSHAKE
+    verdict = lossu[1];
+    if (!grads_out) corr1 = L.loss[2], corr2 = L.loss[3];
+#endif
+  if (verdict == 0u) {   // a timed-out launch stores nothing from here on
+    STAMP(st, ST_VERDICT);
 #ifdef PROBE_STAMPS
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      STAMP(st, ST_LD_ARRIVED);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    STAMP(st, ST_LD_ARRIVED);
 #endif
-      #pragma unroll
-      for (int k = 0; k < 16; ++k) gc[k & 7] += a[k];
-    }
-    for (; w + 8 <= n_wg; w += 8) {
-      float a[8];
-      #pragma unroll
-      for (int k = 0; k < 8; ++k) a[k] = xwg_load(&slabs[(long long)(w + k) * SLAB + i]);
-      #pragma unroll
-      for (int k = 0; k < 8; ++k) gc[k] += a[k];
-    }
-    if (w < n_wg) {
-      float a[7];
-      #pragma unroll
-      for (int k = 0; k < 7; ++k) {
-        a[k] = xwg_load(&slabs[(long long)min(w + k, n_wg - 1) * SLAB + i]);
+    float g;
+    {
+      float gc[8] = {z0, z1, z0, z1, z0, z1, z0, z1};
+      int w;
+      if (n_wg >= 16) {
+        #pragma unroll
+        for (int k = 0; k < 16; ++k) gc[k & 7] += a[k];
+        w = 16;
+      } else {
+        if (n_wg >= 8) {
+          #pragma unroll
+          for (int k = 0; k < 8; ++k) gc[k] += a[k];
+          #pragma unroll
+          for (int k = 0; k < 7; ++k) {
+            if (8 + k < n_wg) gc[0] += a[8 + k];
+          }
+        } else {
+          #pragma unroll
+          for (int k = 0; k < 7; ++k) {
+            if (k < n_wg) gc[0] += a[k];
+          }
+        }
+        w = n_wg;
       }
-      #pragma unroll
-      for (int k = 0; k < 7; ++k) {
-        if (w + k < n_wg) gc[0] += a[k];
-      }
+      stripe_sum_from(gc, slabs, i0, w, n_wg);
+      g = ((gc[0] + gc[1]) + (gc[2] + gc[3])) + ((gc[4] + gc[5]) + (gc[6] + gc[7]));
     }
-    const float g0 = gc[0], g1 = gc[1], g2 = gc[2], g3 = gc[3];
-    const float g4 = gc[4], g5 = gc[5], g6 = gc[6], g7 = gc[7];
-    const float g = ((g0 + g1) + (g2 + g3)) + ((g4 + g5) + (g6 + g7));
-    if (grads_out) {            // reduce-only: hand the summed grads (+loss
-      grads_out[i] = g;         // at NPARAM) to the RCCL all-reduce
-      continue;
-    }
-    if (i == NPARAM) {
+#ifdef PROBE_STAMPS
+    asm volatile("" :: "v"(g));
+    STAMP(st, ST_FOLD);
+#endif
+    if (grads_out) {     // reduce-only: hand the summed grads (+loss
+      grads_out[i0] = g;        // at NPARAM) to the RCCL all-reduce
+    } else if (i0 == NPARAM) {
       *loss_out = g;
-      continue;
+    } else {
+      adam_apply(p0, m0, v0, g, bm0, bv0, lr, beta1, beta2, eps, corr1, corr2);
+#ifdef PROBE_STAMPS
+      asm volatile("" :: "v"(p0));
+      STAMP(st, ST_ADAM);
+#endif
+      m[i0] = m0;
+      v[i0] = v0;
+      master[i0] = p0;
+      const u16 wb = f2bf(p0);
+      bfmirror[i0] = wb;
+      if (nimg >= 1) wimg[t0] = wb;
+      if (nimg == 2) wimg[t1] = wb;
     }
-    const int j = i - lo;
-    float p = use_pre ? pre[j] : master[i];
-    float mi = use_pre ? pre[span_pre + j] : m[i];
-    float vi = use_pre ? pre[2 * span_pre + j] : v[i];
-    adam_update(p, mi, vi, g, lr, beta1, beta2, eps, corr1, corr2);
-    m[i] = mi;
-    v[i] = vi;
-    master[i] = p;
-    const u16 wb = f2bf(p);
-    bfmirror[i] = wb;
-    if (wimg) wimg_write(wimg, i, wb);
+    // second and later passes (grids below 6 workgroups):
+    // the state comes from pre[], or from memory where pre[] cannot hold it
+    for (int i = i0 + STRIPE_STEP; i < hi; i += STRIPE_STEP) {
+      float gc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+      stripe_sum_from(gc, slabs, i, 0, n_wg);
+      const float g2 =
+          ((gc[0] + gc[1]) + (gc[2] + gc[3])) + ((gc[4] + gc[5]) + (gc[6] + gc[7]));
+      if (grads_out) {
+        grads_out[i] = g2;
+        continue;
+      }
+      if (i == NPARAM) {
+        *loss_out = g2;
+        continue;
+      }
+      const int j = i - lo;
+      float p = use_pre ? pre[j] : master[i];
+      float mi = use_pre ? pre[span + j] : m[i];
+      float vi = use_pre ? pre[2 * span + j] : v[i];
+      adam_update(p, mi, vi, g2, lr, beta1, beta2, eps, corr1, corr2);
+      m[i] = mi;
+      v[i] = vi;
+      master[i] = p;
+      const u16 wb = f2bf(p);
+      bfmirror[i] = wb;
+      if (wimg) wimg_write(wimg, i, wb);
+    }
+  }
+  }
+  if (verdict != 0u) {              // timed out: poison the loss, keep going
+    if (tid == 0 && blockIdx.x == 0) *loss_out = __builtin_nanf("");
+    return;
   }
   if (tid == 0 && blockIdx.x == 0) {
     *counter = epoch;
