@@ -29,6 +29,8 @@ ext = CUDAExtension(
     depends=[
         "unionml_amd/ops/hip/bagged_forest.h",
         "unionml_amd/ops/hip/forest.h",
+        "unionml_amd/ops/hip/forest_device.h",
+        "unionml_amd/ops/hip/forest_limits.h",
         "unionml_amd/ops/hip/tabular_common.h",
         "unionml_amd/ops/hip/tabular_gen_tiles.h",
         "unionml_amd/ops/hip/tabular_launch.h",

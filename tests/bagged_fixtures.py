@@ -26,6 +26,8 @@ MODELS = {
     "rf_nan": (RandomForestClassifier, 4, 6, N_TRAIN, 0.1, {"n_estimators": 7}),
     # 79,999 nodes a tree: beyond 16-bit offsets and any LDS prefix
     "et_huge": (ExtraTreesRegressor, 0, 4, 40000, 0.0, {"n_estimators": 2}),
+    # 300 features: the row tile's F > 256 branch at 16 rows a workgroup
+    "wide": (RandomForestClassifier, 3, 300, N_TRAIN, 0.0, {"n_estimators": 5}),
 }
 
 

@@ -1,8 +1,11 @@
 """ForestPredictor on the CPU substrate: packing, rd32 and the sum order
 against sklearn's own fp64 scores, bit for bit."""
 
+import pickle
+
 import numpy as np
 import pytest
+import scipy.sparse
 from forest_fixtures import MODELS, fitted, probe_rows, raw_argmax_labels, sklearn_scores
 from sklearn.ensemble import HistGradientBoostingClassifier, HistGradientBoostingRegressor
 
@@ -51,9 +54,20 @@ def test_refusals():
         forest.predict(X)
     assert np.array_equal(forest.decision_function(X).numpy()[:, 0],
                           poisson._raw_predict(X).ravel())
+    with pytest.raises(ValueError, match="sparse"):
+        forest.decision_function(scipy.sparse.csr_matrix(X))
 
 
 def test_rows_per_wg_is_the_header_table():
     # the literals forest.h holds forest_rows_per_wg to
     assert [rows_per_wg(*fk) for fk in ((64, 10), (64, 32), (5, 1), (300, 3), (2048, 1),
                                         (2049, 1))] == [128, 64, 2048, 32, 4, 0]
+
+
+@pytest.mark.parametrize("app", ["gbdt", "rforest"])
+def test_cache_saved_under_the_apps_path_loads_empty(app):
+    # what an artifact saved before the cache moved to ops/forest.py holds
+    old = b"cunionml_amd.models." + app.encode() + b"\n_ForestCache\n)R."
+    cache = pickle.loads(old)
+    assert (cache.forest, cache.count) == (None, 0)
+    assert pickle.loads(pickle.dumps(cache)).forest is None

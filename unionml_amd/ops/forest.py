@@ -14,17 +14,19 @@ vectorised fp64 traversal; on a GPU machine a missing extension is the usual
 and single ``DecisionTree*`` / ``ExtraTree*`` estimators (the format of
 ``hip/bagged_forest.h``, ``bagged_forest_predict_kernel``): ``predict_proba``
 / ``predict`` equal sklearn's at ``n_jobs=None`` bit for bit. The module's
-``from_sklearn(est)`` returns the predictor that fits the estimator.
+``from_sklearn(est)`` returns the predictor that fits the estimator, and
+``device_forest(est)`` keeps it on the estimator for the apps. What the two
+predictors share (device, upload, input check, output handling) is
+``_PackedForest``.
 """
-
-from collections import deque
 
 import numpy as np
 import torch
 
 from unionml_amd.ops import hip_ext
 
-# the Python copy of hip/forest.h (a GPU test holds the two equal)
+# the Python copy of hip/forest_limits.h and hip/forest.h (a GPU test holds
+# the two equal)
 MAX_CLASSES = 32
 MAX_FEATURES = 2048
 CHUNK_NODES = 2048          # the most nodes one tree may have: one LDS chunk
@@ -47,31 +49,45 @@ def rd32(t):
     return np.where(up, np.nextafter(f, np.float32(-np.inf)), f).astype(np.float32)
 
 
-def rows_per_wg(n_features: int, n_scores: int) -> int:
-    """Rows per workgroup: the largest power of two whose fp32 tile (odd row
-    stride) fits the carve and whose rows x classes fit 8 items a thread."""
+def _tile_rows(n_features, n_scores, max_rows, tile_bytes, max_items):
+    """forest_tile_rows of hip/forest_limits.h: the largest power of two in
+    MIN_ROWS..max_rows whose fp32 tile (odd row stride) fits ``tile_bytes``
+    and whose rows x scores fit ``max_items``; 0 when F or K is out of range."""
     if not (1 <= n_features <= MAX_FEATURES and 1 <= n_scores <= MAX_CLASSES):
         return 0
-    R = MAX_ROWS
-    while R > MIN_ROWS and (R * (n_features | 1) * 4 > TILE_BYTES
-                            or R * n_scores > BLOCK * MAX_ITEMS):
+    R = max_rows
+    while R > MIN_ROWS and (R * (n_features | 1) * 4 > tile_bytes or R * n_scores > max_items):
         R //= 2
     return R
 
 
-def _pack_tree(nodes):
-    """One sklearn tree -> packed nodes, renumbered breadth-first so that a
-    node's children are adjacent; a leaf points at itself behind thr = +inf
-    with the missing-goes-left bit set."""
-    order, queue = [], deque([0])
-    while queue:
-        i = queue.popleft()
-        order.append(i)
-        if not nodes["is_leaf"][i]:
-            queue.extend((int(nodes["left"][i]), int(nodes["right"][i])))
-    order = np.asarray(order)
-    new_of = np.empty(len(nodes), dtype=np.int64)
+def rows_per_wg(n_features: int, n_scores: int) -> int:
+    """Rows per workgroup of the boosted kernel: up to 2,048, rows x classes
+    within 8 items a thread."""
+    return _tile_rows(n_features, n_scores, MAX_ROWS, TILE_BYTES, BLOCK * MAX_ITEMS)
+
+
+def _breadth_first(left, right, inner):
+    """A tree's nodes (root 0, ``inner`` marking those with children) in
+    breadth-first order, level by level, so that a node's children end up
+    adjacent -> (old index of each new node, new index of each old node)."""
+    levels, level = [], np.zeros(1, dtype=np.int64)
+    while level.size:
+        levels.append(level)
+        parents = level[inner[level]]
+        level = np.stack([left[parents], right[parents]], axis=1).reshape(-1).astype(np.int64)
+    order = np.concatenate(levels)
+    assert len(order) == len(inner)
+    new_of = np.empty(len(order), dtype=np.int64)
     new_of[order] = np.arange(len(order))
+    return order, new_of
+
+
+def _pack_tree(nodes):
+    """One sklearn tree -> packed nodes, renumbered breadth-first; a leaf
+    points at itself behind thr = +inf with the missing-goes-left bit set."""
+    order, new_of = _breadth_first(nodes["left"], nodes["right"],
+                                   ~nodes["is_leaf"].astype(bool))
     src = nodes[order]
     leaf = src["is_leaf"].astype(bool)
     out = np.zeros(len(order), dtype=NODE_DTYPE)
@@ -86,46 +102,92 @@ def _pack_tree(nodes):
     return out
 
 
-class ForestPredictor:
-    """A packed forest on one device. Build with :meth:`from_sklearn`."""
+class _PackedForest:
+    """What the two predictors do alike: a packed forest's nodes and tree
+    table on one device, the check of the rows, and the outputs around the
+    kernel (or, without a GPU, around the host walk). A predictor adds its
+    own third array, ``_launch`` (the kernel) and ``_host`` (the walk)."""
 
-    def __init__(self, nodes, tree_first, baseline, n_features, classes=None,
-                 identity_link=True, device=None):
+    def __init__(self, nodes, tree_first, n_features, n_scores, classes, device):
         if device is None:
             device = "cuda" if torch.cuda.is_available() else "cpu"
         self.device = torch.device(device)
         self.n_features = int(n_features)
-        self.n_scores = int(len(baseline))
+        self.n_scores = int(n_scores)
         self.n_trees = int(len(tree_first) - 1)
         self.max_tree_nodes = int(np.diff(tree_first).max())
-        self.rows_per_wg = rows_per_wg(self.n_features, self.n_scores)
         self.classes_ = None if classes is None else np.asarray(classes)
-        self.identity_link = bool(identity_link)
-        self._nodes_np, self._first_np, self._baseline_np = nodes, tree_first, baseline
+        self._nodes_np, self._first_np = nodes, tree_first
         self._ext = None
         if self.device.type == "cuda":
             self._ext = hip_ext(required=True)
-            self._nodes = torch.from_numpy(nodes.view("<i4").reshape(-1, 4)).to(self.device)
+            words = nodes.dtype.itemsize // 4
+            self._nodes = torch.from_numpy(nodes.view("<i4").reshape(-1, words)).to(self.device)
             self._first = torch.from_numpy(tree_first).to(self.device)
-            self._baseline = torch.from_numpy(baseline).to(self.device)
+
+    def _upload(self, array):
+        """The predictor's own array on the device (None without a GPU)."""
+        return None if self._ext is None else torch.from_numpy(array).to(self.device)
+
+    @staticmethod
+    def _refuse_beyond_limits(K, what, F, n_nodes):
+        """The refusals of ``from_sklearn`` that both kernels share."""
+        if not 1 <= K <= MAX_CLASSES:
+            raise ValueError(f"{K} {what}: the kernel takes 1..{MAX_CLASSES}")
+        if F > MAX_FEATURES:
+            raise ValueError(f"{F} features: the row tile takes at most {MAX_FEATURES}")
+        if n_nodes > 1 << 30:
+            raise ValueError("the forest has more than 2^30 nodes")
+
+    def _rows(self, X):
+        if hasattr(X, "tocsr"):
+            raise ValueError("a sparse X is not supported: pass a dense float [B][F]")
+        if not torch.is_tensor(X):
+            X = torch.as_tensor(np.asarray(X))
+        if X.dim() != 2 or X.shape[1] != self.n_features or not X.is_floating_point():
+            raise ValueError(f"X must be a float [B][{self.n_features}], is {tuple(X.shape)} "
+                             f"{X.dtype}")
+        return X.to(self.device, torch.float32).contiguous()
+
+    def _run(self, X, *caps):
+        """-> (fp64 [B][K], class indices int32 [B]) on the device, from the
+        kernel under ``caps`` or from the host walk."""
+        X = self._rows(X)
+        B = X.shape[0]
+        out = torch.empty(B, self.n_scores, dtype=torch.float64, device=self.device)
+        labels = torch.empty(B, dtype=torch.int32, device=self.device)
+        if B == 0:
+            return out, labels
+        if self._ext is not None:
+            self._launch(X, out, labels, *caps)
+            return out, labels
+        values, idx = self._host(X.numpy())
+        out.copy_(torch.from_numpy(values))
+        labels.copy_(torch.from_numpy(idx.astype(np.int32)))
+        return out, labels
+
+
+class ForestPredictor(_PackedForest):
+    """A packed forest on one device. Build with :meth:`from_sklearn`."""
+
+    def __init__(self, nodes, tree_first, baseline, n_features, classes=None,
+                 identity_link=True, device=None):
+        super().__init__(nodes, tree_first, n_features, len(baseline), classes, device)
+        self.rows_per_wg = rows_per_wg(self.n_features, self.n_scores)
+        self.identity_link = bool(identity_link)
+        self._baseline_np, self._baseline = baseline, self._upload(baseline)
 
     @classmethod
     def from_sklearn(cls, est, device=None):
         predictors = est._predictors
-        K = len(predictors[0])
-        if not 1 <= K <= MAX_CLASSES:
-            raise ValueError(f"{K} trees per iteration: the kernel takes 1..{MAX_CLASSES}")
-        F = int(est.n_features_in_)
-        if F > MAX_FEATURES:
-            raise ValueError(f"{F} features: the row tile takes at most {MAX_FEATURES}")
+        K, F = len(predictors[0]), int(est.n_features_in_)
         trees = [tree.nodes for iteration in predictors for tree in iteration]
+        cls._refuse_beyond_limits(K, "trees per iteration", F, sum(len(t) for t in trees))
         if any(t["is_categorical"].any() for t in trees):
             raise ValueError("categorical splits are not supported by the forest kernel")
         largest = max(len(t) for t in trees)
         if largest > CHUNK_NODES:
             raise ValueError(f"a tree has {largest} nodes: one LDS chunk holds {CHUNK_NODES}")
-        if sum(len(t) for t in trees) > 1 << 30:
-            raise ValueError("the forest has more than 2^30 nodes")
         nodes = np.concatenate([_pack_tree(t) for t in trees])
         tree_first = np.concatenate([[0], np.cumsum([len(t) for t in trees])]).astype(np.int32)
         # sklearn starts from zeros + baseline
@@ -137,30 +199,17 @@ class ForestPredictor:
 
     # -- scoring ----------------------------------------------------------------
 
-    def _rows(self, X):
-        X = torch.as_tensor(np.asarray(X) if not torch.is_tensor(X) else X)
-        if X.dim() != 2 or X.shape[1] != self.n_features or not X.is_floating_point():
-            raise ValueError(f"X must be a float [B][{self.n_features}], is {tuple(X.shape)} "
-                             f"{X.dtype}")
-        return X.to(self.device, torch.float32).contiguous()
-
     def _score(self, X, trees_per_chunk=0):
         """-> (scores fp64 [B][K], class indices int32 [B]) on the device."""
-        X = self._rows(X)
-        B, K = X.shape[0], self.n_scores
-        scores = torch.empty(B, K, dtype=torch.float64, device=self.device)
-        labels = torch.empty(B, dtype=torch.int32, device=self.device)
-        if B == 0:
-            return scores, labels
-        if self._ext is not None:
-            self._ext.forest_predict(X, self._nodes, self._first, self._baseline,
-                                     self.max_tree_nodes, scores, labels, trees_per_chunk)
-            return scores, labels
-        s, _ = self._walk_cpu(X.numpy())
-        scores.copy_(torch.from_numpy(s))
-        idx = (s[:, 0] > 0) if K == 1 else s.argmax(axis=1)   # first of the largest
-        labels.copy_(torch.from_numpy(idx.astype(np.int32)))
-        return scores, labels
+        return self._run(X, trees_per_chunk)
+
+    def _launch(self, X, scores, labels, trees_per_chunk):
+        self._ext.forest_predict(X, self._nodes, self._first, self._baseline,
+                                 self.max_tree_nodes, scores, labels, trees_per_chunk)
+
+    def _host(self, X):
+        s, _ = self._walk_cpu(X)
+        return s, (s[:, 0] > 0) if self.n_scores == 1 else s.argmax(axis=1)   # first largest
 
     def _walk_cpu(self, X):
         """The packed arrays walked on the host, tree by tree in the kernel's
@@ -235,16 +284,10 @@ BAGGED_META_MISSING_LEFT, BAGGED_META_DIST_SHIFT = 1 << 11, 12
 
 
 def bagged_rows_per_wg(n_features: int, n_scores: int) -> int:
-    """Rows per workgroup of the bagged kernel: the largest power of two in
-    4..256 whose fp32 tile (odd row stride) fits the carve and whose rows x
-    values fit 2,048 sums."""
-    if not (1 <= n_features <= MAX_FEATURES and 1 <= n_scores <= MAX_CLASSES):
-        return 0
-    R = BAGGED_MAX_ROWS
-    while R > BAGGED_MIN_ROWS and (R * (n_features | 1) * 4 > BAGGED_TILE_BYTES
-                                   or R * n_scores > BAGGED_MAX_ITEMS):
-        R //= 2
-    return R
+    """Rows per workgroup of the bagged kernel: up to 256, rows x values
+    within 2,048 sums."""
+    return _tile_rows(n_features, n_scores, BAGGED_MAX_ROWS, BAGGED_TILE_BYTES,
+                      BAGGED_MAX_ITEMS)
 
 
 def bagged_trees_per_chunk(rows: int, n_trees: int, cap: int = 0) -> int:
@@ -258,20 +301,11 @@ def bagged_trees_per_chunk(rows: int, n_trees: int, cap: int = 0) -> int:
 
 def _pack_bagged_tree(tree, first_leaf_row):
     """One sklearn ``Tree`` -> (packed nodes, leaf values [leaves][K]),
-    renumbered breadth-first, level by level, so that a node's children are
-    adjacent; leaves number the rows of leaf_values from ``first_leaf_row``
-    in that order."""
+    renumbered breadth-first; leaves number the rows of leaf_values from
+    ``first_leaf_row`` in that order."""
     left, right = tree.children_left, tree.children_right
-    levels, level = [], np.zeros(1, dtype=np.int64)
-    while level.size:
-        levels.append(level)
-        inner = level[left[level] >= 0]
-        level = np.stack([left[inner], right[inner]], axis=1).reshape(-1)
-    order = np.concatenate(levels)
+    order, new_of = _breadth_first(left, right, left >= 0)
     n = len(order)
-    assert n == tree.node_count
-    new_of = np.empty(n, dtype=np.int64)
-    new_of[order] = np.arange(n)
     leaf = left[order] < 0
     dist = np.where(leaf, 0, new_of[np.where(leaf, 0, left[order])] - np.arange(n))
     assert np.all(leaf | (new_of[right[order]] == np.arange(n) + dist + 1))
@@ -297,29 +331,16 @@ def _is_bagged(est) -> bool:
                             tree.DecisionTreeClassifier, tree.DecisionTreeRegressor))
 
 
-class BaggedForestPredictor:
+class BaggedForestPredictor(_PackedForest):
     """A packed random forest, extra-trees ensemble or single decision tree
     on one device: the mean over the trees of the leaves' fp64 vectors, in
     sklearn's ``n_jobs=None`` order, bit for bit (docs/kernels.md
     "Bagged-forest inference"). Build with :meth:`from_sklearn`."""
 
     def __init__(self, nodes, tree_first, leaf_values, n_features, classes=None, device=None):
-        if device is None:
-            device = "cuda" if torch.cuda.is_available() else "cpu"
-        self.device = torch.device(device)
-        self.n_features = int(n_features)
-        self.n_scores = int(leaf_values.shape[1])
-        self.n_trees = int(len(tree_first) - 1)
-        self.max_tree_nodes = int(np.diff(tree_first).max())
+        super().__init__(nodes, tree_first, n_features, leaf_values.shape[1], classes, device)
         self.rows_per_wg = bagged_rows_per_wg(self.n_features, self.n_scores)
-        self.classes_ = None if classes is None else np.asarray(classes)
-        self._nodes_np, self._first_np, self._values_np = nodes, tree_first, leaf_values
-        self._ext = None
-        if self.device.type == "cuda":
-            self._ext = hip_ext(required=True)
-            self._nodes = torch.from_numpy(nodes.view("<i4").reshape(-1, 2)).to(self.device)
-            self._first = torch.from_numpy(tree_first).to(self.device)
-            self._values = torch.from_numpy(leaf_values).to(self.device)
+        self._values_np, self._values = leaf_values, self._upload(leaf_values)
 
     @classmethod
     def from_sklearn(cls, est, device=None):
@@ -330,17 +351,11 @@ class BaggedForestPredictor:
         if int(est.n_outputs_) > 1:
             raise ValueError(f"{est.n_outputs_} outputs: the bagged kernel takes one")
         classes = getattr(est, "classes_", None)
-        K = 1 if classes is None else len(classes)
-        if not 1 <= K <= MAX_CLASSES:
-            raise ValueError(f"{K} classes: the kernel takes 1..{MAX_CLASSES}")
-        F = int(est.n_features_in_)
-        if F > MAX_FEATURES:
-            raise ValueError(f"{F} features: the row tile takes at most {MAX_FEATURES}")
+        K, F = 1 if classes is None else len(classes), int(est.n_features_in_)
+        cls._refuse_beyond_limits(K, "classes", F, sum(t.node_count for t in trees))
         largest = max(t.node_count for t in trees)
         if largest > BAGGED_MAX_TREE_NODES:
             raise ValueError(f"a tree has {largest} nodes: a child distance has 20 bits")
-        if sum(t.node_count for t in trees) > 1 << 30:
-            raise ValueError("the forest has more than 2^30 nodes")
         packed, first_leaf_row = [], 0
         for t in trees:
             packed.append(_pack_bagged_tree(t, first_leaf_row))
@@ -353,32 +368,18 @@ class BaggedForestPredictor:
 
     # -- scoring ----------------------------------------------------------------
 
-    def _rows(self, X):
-        if hasattr(X, "tocsr"):
-            raise ValueError("a sparse X is not supported: pass a dense float [B][F]")
-        X = torch.as_tensor(np.asarray(X) if not torch.is_tensor(X) else X)
-        if X.dim() != 2 or X.shape[1] != self.n_features or not X.is_floating_point():
-            raise ValueError(f"X must be a float [B][{self.n_features}], is {tuple(X.shape)} "
-                             f"{X.dtype}")
-        return X.to(self.device, torch.float32).contiguous()
-
     def _score(self, X, prefix_nodes=-1, trees_per_chunk=0):
         """-> (means fp64 [B][K], class indices int32 [B]) on the device."""
-        X = self._rows(X)
-        B, K = X.shape[0], self.n_scores
-        probs = torch.empty(B, K, dtype=torch.float64, device=self.device)
-        labels = torch.empty(B, dtype=torch.int32, device=self.device)
-        if B == 0:
-            return probs, labels
-        if self._ext is not None:
-            self._ext.bagged_forest_predict(X, self._nodes, self._first, self._values,
-                                            self.max_tree_nodes, probs, labels,
-                                            prefix_nodes, trees_per_chunk)
-            return probs, labels
-        p = self._walk_cpu(X.numpy())
-        probs.copy_(torch.from_numpy(p))
-        labels.copy_(torch.from_numpy(p.argmax(axis=1).astype(np.int32)))   # first largest
-        return probs, labels
+        return self._run(X, prefix_nodes, trees_per_chunk)
+
+    def _launch(self, X, probs, labels, prefix_nodes, trees_per_chunk):
+        self._ext.bagged_forest_predict(X, self._nodes, self._first, self._values,
+                                        self.max_tree_nodes, probs, labels, prefix_nodes,
+                                        trees_per_chunk)
+
+    def _host(self, X):
+        p = self._walk_cpu(X)
+        return p, p.argmax(axis=1)   # first largest
 
     def _leaves_cpu(self, X, t):
         """leaf_values rows that the rows of X reach in tree t."""
@@ -434,3 +435,33 @@ def from_sklearn(est, device=None):
     if _is_bagged(est):
         return BaggedForestPredictor.from_sklearn(est, device=device)
     raise TypeError(f"no device predictor for {type(est).__name__}")
+
+
+class _ForestCache:
+    """The packed forest of a fitted estimator, kept on the estimator object.
+    Valid while the estimator holds the same list of trees (``_predictors``
+    of a boosted estimator, ``estimators_`` of a bagged one) at the same
+    length: a refit makes a new list, a warm start extends it. Pickles as an
+    empty cache, so that a saved artifact holds no device memory."""
+
+    def __init__(self):
+        self.trees, self.count, self.forest = None, 0, None
+
+    def __reduce__(self):
+        return (_ForestCache, ())
+
+    def get(self, est):
+        trees = est._predictors if hasattr(est, "_predictors") else est.estimators_
+        if self.trees is not trees or self.count != len(trees):
+            self.forest = from_sklearn(est)
+            self.trees, self.count = trees, len(trees)
+        return self.forest
+
+
+def device_forest(est):
+    """The device predictor of a fitted boosted or bagged ensemble, built
+    once per fit and kept on the estimator."""
+    cache = getattr(est, "_unionml_forest", None)
+    if cache is None:
+        cache = est._unionml_forest = _ForestCache()
+    return cache.get(est)

@@ -25,6 +25,8 @@
 
 #include <hip/hip_runtime_api.h>
 
+#include "forest_limits.h"
+
 struct BaggedNode {
   float thr;       // rd32(threshold): x <= t in fp64  <=>  x <= thr in fp32;
                    // a leaf: the bits of its leaf_values row (uint32)
@@ -32,12 +34,9 @@ struct BaggedNode {
 };
 static_assert(sizeof(BaggedNode) == 8, "one 8-byte load per visit");
 
-constexpr int BAGGED_BLOCK = 256;
-constexpr int BAGGED_MAX_CLASSES = 32;
-constexpr int BAGGED_MAX_FEATURES = 2048;          // 11 bits of meta
+static_assert(FOREST_MAX_FEATURES <= 1 << 11, "a node's feature has 11 bits of meta");
 constexpr int BAGGED_MAX_TREE_NODES = 1 << 20;     // 20 bits of distance
-constexpr int BAGGED_MIN_ROWS = 4;                 // rows per workgroup: a power of two,
-constexpr int BAGGED_MAX_ROWS = 256;               // BAGGED_MIN_ROWS..BAGGED_MAX_ROWS
+constexpr int BAGGED_MAX_ROWS = 256;               // the most rows per workgroup
 constexpr int BAGGED_META_MISSING_LEFT = 1 << 11;
 constexpr int BAGGED_META_DIST_SHIFT = 12;
 
@@ -49,9 +48,7 @@ constexpr int BAGGED_META_DIST_SHIFT = 12;
 //                    of the chunk gives row r, BAGGED_WALK_ITEMS of them
 //   [40960, 45056)   two tree tables (this chunk's and the next one's), each
 //                    BAGGED_CHUNK_TREES first nodes and as many node counts
-//   [45056, ...)     the row tile [R][F | 1] fp32
-// The whole carve stays within BAGGED_LDS_BUDGET so that two workgroups
-// share a CU's 160 KiB.
+//   [45056, ...)     the row tile [R][F | 1] fp32, within FOREST_LDS_BUDGET
 constexpr int BAGGED_PREFIX_SLOTS = 2048;
 constexpr int BAGGED_MAX_ITEMS = 2048;     // R * K <= this: (row, class) sums
 constexpr int BAGGED_WALK_ITEMS = 2048;    // RP * C <= this: (row, tree) walks of a chunk
@@ -60,33 +57,25 @@ constexpr int BAGGED_LDS_ACC_OFF = BAGGED_PREFIX_SLOTS * 8;
 constexpr int BAGGED_LDS_LEAF_OFF = BAGGED_LDS_ACC_OFF + BAGGED_MAX_ITEMS * 8;
 constexpr int BAGGED_LDS_TAB_OFF = BAGGED_LDS_LEAF_OFF + BAGGED_WALK_ITEMS * 4;
 constexpr int BAGGED_LDS_TILE_OFF = BAGGED_LDS_TAB_OFF + 2 * 2 * BAGGED_CHUNK_TREES * 4;
-constexpr int BAGGED_LDS_BUDGET = 80 * 1024;
-constexpr int BAGGED_TILE_BYTES = BAGGED_LDS_BUDGET - BAGGED_LDS_TILE_OFF;
+constexpr int BAGGED_TILE_BYTES = FOREST_LDS_BUDGET - BAGGED_LDS_TILE_OFF;
 
 static_assert(BAGGED_LDS_TILE_OFF == 45056 && BAGGED_TILE_BYTES == 36864, "the carve above");
-static_assert(2 * BAGGED_LDS_BUDGET <= 160 * 1024, "two workgroups share a CU");
-static_assert(BAGGED_PREFIX_SLOTS % BAGGED_BLOCK == 0 && BAGGED_CHUNK_TREES == BAGGED_BLOCK,
+static_assert(BAGGED_PREFIX_SLOTS % FOREST_BLOCK == 0 && BAGGED_CHUNK_TREES == FOREST_BLOCK,
               "a thread prefetches PREFIX_SLOTS / BLOCK nodes and one table entry");
-static_assert(BAGGED_MAX_ROWS * BAGGED_MAX_CLASSES >= BAGGED_MAX_ITEMS &&
-                  BAGGED_MIN_ROWS * BAGGED_MAX_CLASSES <= BAGGED_MAX_ITEMS,
+static_assert(BAGGED_MAX_ROWS * FOREST_MAX_CLASSES >= BAGGED_MAX_ITEMS &&
+                  FOREST_MIN_ROWS * FOREST_MAX_CLASSES <= BAGGED_MAX_ITEMS,
               "the widest K fits at the smallest R");
 static_assert(BAGGED_MAX_ROWS <= BAGGED_WALK_ITEMS, "a chunk holds at least one tree");
-static_assert(BAGGED_MIN_ROWS * ((BAGGED_MAX_FEATURES | 1) * 4) <= BAGGED_TILE_BYTES,
+static_assert(FOREST_MIN_ROWS * (forest_row_stride(FOREST_MAX_FEATURES) * 4) <= BAGGED_TILE_BYTES,
               "the widest row fits at the smallest R");
-static_assert(BAGGED_MAX_ITEMS * BAGGED_MAX_CLASSES < (1 << 20),
+static_assert(BAGGED_MAX_ITEMS * FOREST_MAX_CLASSES < (1 << 20),
               "i / K by a 20-bit multiplier is exact for i < BAGGED_MAX_ITEMS");
 
-// Rows per workgroup for F features and K values a leaf: the largest power
-// of two in BAGGED_MIN_ROWS..BAGGED_MAX_ROWS whose fp32 tile (odd row
-// stride) fits BAGGED_TILE_BYTES and whose R * K sums fit BAGGED_MAX_ITEMS.
-// 0: none (F or K out of range).
+// Rows per workgroup for F features and K values a leaf (forest_tile_rows):
+// up to BAGGED_MAX_ROWS, the tile within BAGGED_TILE_BYTES and the R * K
+// sums within BAGGED_MAX_ITEMS.
 constexpr int bagged_rows_per_wg(int F, int K) {
-  if (F < 1 || F > BAGGED_MAX_FEATURES || K < 1 || K > BAGGED_MAX_CLASSES) return 0;
-  int R = BAGGED_MAX_ROWS;
-  while (R > BAGGED_MIN_ROWS &&
-         (R * (F | 1) * 4 > BAGGED_TILE_BYTES || R * K > BAGGED_MAX_ITEMS))
-    R >>= 1;
-  return R;
+  return forest_tile_rows(F, K, BAGGED_MAX_ROWS, BAGGED_TILE_BYTES, BAGGED_MAX_ITEMS);
 }
 static_assert(bagged_rows_per_wg(64, 10) == 128 && bagged_rows_per_wg(64, 32) == 64 &&
                   bagged_rows_per_wg(5, 2) == 256 && bagged_rows_per_wg(300, 3) == 16 &&

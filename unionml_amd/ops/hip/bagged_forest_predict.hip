@@ -53,11 +53,12 @@
 #include <hip/hip_runtime.h>
 
 #include "bagged_forest.h"
+#include "forest_device.h"
 #include "tabular_launch.h"
 
 namespace {
 
-constexpr int PRE = BAGGED_PREFIX_SLOTS / BAGGED_BLOCK;   // prefetched nodes per thread
+constexpr int PRE = BAGGED_PREFIX_SLOTS / FOREST_BLOCK;   // prefetched nodes per thread
 constexpr int AHEAD = 8;                                  // leaf-value loads in flight
 
 typedef unsigned v2u __attribute__((ext_vector_type(2)));   // a BaggedNode as a native vector
@@ -69,7 +70,6 @@ struct ChunkRegs {
   int first, count;
 };
 static_assert(PRE == 8, "ChunkRegs names eight nodes");
-#define BAGGED_EACH_NODE(X) X(0, n0) X(1, n1) X(2, n2) X(3, n3) X(4, n4) X(5, n5) X(6, n6) X(7, n7)
 
 // Table entry of tree t: its first node, clamped into the node array, and
 // its node count, clamped to what the array holds behind it and to the
@@ -99,12 +99,12 @@ __device__ __forceinline__ void issue_chunk(ChunkRegs& r, const v2u* __restrict_
   const int ps_mask = (1 << ps_shift) - 1;
 #define BAGGED_ISSUE(J, N)                                              \
   {                                                                     \
-    const int e = tid + J * BAGGED_BLOCK;                               \
+    const int e = tid + J * FOREST_BLOCK;                               \
     const int s = e >> ps_shift;                                        \
     const int p = tab_first[s < BAGGED_CHUNK_TREES ? s : BAGGED_CHUNK_TREES - 1] + (e & ps_mask); \
     r.N = nodes[p < last ? p : last];                                   \
   }
-  BAGGED_EACH_NODE(BAGGED_ISSUE)
+  FOREST_EACH_NODE(BAGGED_ISSUE)
 #undef BAGGED_ISSUE
 }
 
@@ -117,16 +117,16 @@ __device__ __forceinline__ void store_chunk(const ChunkRegs& r, v2u* s_nodes,
   const int ps_mask = (1 << ps_shift) - 1;
 #define BAGGED_STORE(J, N)                                              \
   {                                                                     \
-    const int e = tid + J * BAGGED_BLOCK;                               \
+    const int e = tid + J * FOREST_BLOCK;                               \
     const int s = e >> ps_shift, j = e & ps_mask;                       \
     if (s < nt && j < P && j < tab_count[s]) s_nodes[e] = r.N;          \
   }
-  BAGGED_EACH_NODE(BAGGED_STORE)
+  FOREST_EACH_NODE(BAGGED_STORE)
 #undef BAGGED_STORE
 }
 
 template <int U>
-__global__ void __launch_bounds__(BAGGED_BLOCK)
+__global__ void __launch_bounds__(FOREST_BLOCK)
 bagged_forest_predict_kernel(const float* __restrict__ X,             // [B][F]
                              const v2u* __restrict__ nodes,           // [n_nodes] BaggedNode
                              const int* __restrict__ tree_first,      // [T + 1]
@@ -153,7 +153,7 @@ bagged_forest_predict_kernel(const float* __restrict__ X,             // [B][F]
 
   const int tid = threadIdx.x;
   const int R = 1 << rshift;
-  const int stride = F | 1;
+  const int stride = forest_row_stride(F);
   const long long row0 = (long long)blockIdx.x << rshift;
   const int nrows = B - row0 < R ? (int)(B - row0) : R;
 
@@ -175,50 +175,15 @@ bagged_forest_predict_kernel(const float* __restrict__ X,             // [B][F]
     tab_count(0)[tid] = c0;
     tab_first(1)[tid] = f1;
     tab_count(1)[tid] = c1;
-    for (int i = tid; i < BAGGED_MAX_ITEMS; i += BAGGED_BLOCK) s_acc[i] = 0.0;
+    for (int i = tid; i < BAGGED_MAX_ITEMS; i += FOREST_BLOCK) s_acc[i] = 0.0;
   }
   __syncthreads();
 
   ChunkRegs regs;
   issue_chunk(regs, nodes, tab_first(0), ps_shift, n_nodes, tid);
 
-  // ---- the row tile, while chunk 0 is in flight -------------------------------
-  // element e = row * F + col of the workgroup's contiguous block goes to
-  // s_rows[row * stride + col]; a thread takes e = tid, tid + 256, ... and
-  // moves (row, col) on by 256 elements with an add and a compare. Four
-  // loads are in flight before the first LDS store; they are unconditional
-  // (past the end they re-read the block's last element), the stores are
-  // predicated.
-  {
-    const float* __restrict__ Xw = X + (size_t)row0 * (size_t)F;
-    const int n = nrows * F;
-    int e = tid;
-    int row = (int)(((unsigned)tid * (unsigned)f_magic) >> 20);
-    int col = tid - row * F;
-    auto fetch = [&](float& v, int& at) {
-      v = Xw[e < n ? e : n - 1];
-      at = row * stride + col;
-      e += BAGGED_BLOCK;
-      row += step_rows;
-      col += step_cols;
-      if (col >= F) {
-        col -= F;
-        ++row;
-      }
-    };
-    for (int e0 = tid; e0 - tid < n; e0 += 4 * BAGGED_BLOCK) {
-      float v0, v1, v2, v3;
-      int a0, a1, a2, a3;
-      fetch(v0, a0);
-      fetch(v1, a1);
-      fetch(v2, a2);
-      fetch(v3, a3);
-      if (e0 < n) s_rows[a0] = v0;
-      if (e0 + BAGGED_BLOCK < n) s_rows[a1] = v1;
-      if (e0 + 2 * BAGGED_BLOCK < n) s_rows[a2] = v2;
-      if (e0 + 3 * BAGGED_BLOCK < n) s_rows[a3] = v3;
-    }
-  }
+  // the row tile, while chunk 0 is in flight
+  forest_stage_rows(s_rows, X, row0, nrows, F, stride, f_magic, step_rows, step_cols, tid);
 
   store_chunk(regs, s_nodes, tab_count(0), ps_shift, P, T < C ? T : C, tid);
   __syncthreads();
@@ -240,13 +205,13 @@ bagged_forest_predict_kernel(const float* __restrict__ X,             // [B][F]
 
     // ---- walk: items (row, tree of the chunk), U of a thread at a time ---------
     const int n_walks = nt << rs;
-    for (int j0 = 0; j0 < n_walks; j0 += U * BAGGED_BLOCK) {
+    for (int j0 = 0; j0 < n_walks; j0 += U * FOREST_BLOCK) {
       int base[U], cnt[U], slot[U], idx[U], rowb[U], leaf[U];
       bool live[U], todo[U];
       bool busy = false;
 #pragma unroll
       for (int u = 0; u < U; ++u) {
-        const int j = j0 + u * BAGGED_BLOCK + tid;
+        const int j = j0 + u * FOREST_BLOCK + tid;
         const int row = j & ((1 << rs) - 1), tc = j >> rs;
         live[u] = tc < nt && row < nrows;
         const int tcl = tc < nt ? tc : nt - 1;
@@ -300,7 +265,7 @@ bagged_forest_predict_kernel(const float* __restrict__ X,             // [B][F]
       }
 #pragma unroll
       for (int u = 0; u < U; ++u) {
-        const int j = j0 + u * BAGGED_BLOCK + tid;
+        const int j = j0 + u * FOREST_BLOCK + tid;
         const int l = leaf[u] < 0 ? 0 : (leaf[u] > max_leaf ? max_leaf : leaf[u]);
         if (live[u]) s_leaf[j] = l;   // j == tc * RP + row
       }
@@ -309,7 +274,7 @@ bagged_forest_predict_kernel(const float* __restrict__ X,             // [B][F]
     __syncthreads();   // the chunk's last walker; leaf_idx is complete
 
     // ---- sum: items (row, class), the chunk's trees in order ------------------
-    for (int i = tid; i < n_sums; i += BAGGED_BLOCK) {
+    for (int i = tid; i < n_sums; i += FOREST_BLOCK) {
       const int row = (int)(((unsigned)i * (unsigned)k_magic) >> 20);
       const int k = i - row * K;
       double acc = s_acc[i];
@@ -339,42 +304,27 @@ bagged_forest_predict_kernel(const float* __restrict__ X,             // [B][F]
   // ---- the mean, contiguous stores, and one lane a row for the label ----------
   const double trees = (double)T;
   double* __restrict__ out = probs + (size_t)row0 * (size_t)K;
-  for (int i = tid; i < n_sums; i += BAGGED_BLOCK) {
+  for (int i = tid; i < n_sums; i += FOREST_BLOCK) {
     const double p = s_acc[i] / trees;
     s_acc[i] = p;
     out[i] = p;
   }
   __syncthreads();
-  for (int r = tid; r < nrows; r += BAGGED_BLOCK) {
-    const double* s = s_acc + r * K;
-    int best = 0;
-    double top = s[0];
-    for (int k = 1; k < K; ++k) {
-      const double v = s[k];
-      if (v > top) {   // strict: ties stay with the lowest class
-        top = v;
-        best = k;
-      }
-    }
-    labels[row0 + r] = best;
-  }
+  for (int r = tid; r < nrows; r += FOREST_BLOCK)
+    labels[row0 + r] = forest_first_largest(s_acc + r * K, K);
 }
 
 template <int U>
 int launch_walks(const float* X, int B, int F, int K, const BaggedNode* nodes, int n_nodes,
                  const int* tree_first, int T, const double* leaf_values, int n_leaves,
-                 int p_cap, int c_cap, double* probs, int* labels, int rshift,
-                 hipStream_t stream) {
-  if (ensure_dynamic_lds<bagged_forest_predict_kernel<U>>(BAGGED_LDS_BUDGET) != 0) return -2;
-  const int R = 1 << rshift;
-  const int lds = BAGGED_LDS_TILE_OFF + R * (F | 1) * 4;
-  const long long blocks = ((long long)B + R - 1) >> rshift;
-  hipLaunchKernelGGL(bagged_forest_predict_kernel<U>, dim3((unsigned)blocks),
-                     dim3(BAGGED_BLOCK), lds, stream, X,
+                 int p_cap, int c_cap, double* probs, int* labels,
+                 const ForestTileLaunch& g, hipStream_t stream) {
+  if (ensure_dynamic_lds<bagged_forest_predict_kernel<U>>(FOREST_LDS_BUDGET) != 0) return -2;
+  hipLaunchKernelGGL(bagged_forest_predict_kernel<U>, dim3(g.blocks), dim3(FOREST_BLOCK),
+                     BAGGED_LDS_TILE_OFF + g.tile_bytes, stream, X,
                      reinterpret_cast<const v2u*>(nodes), tree_first, leaf_values, probs,
-                     labels, B, F, K, T, n_nodes, n_leaves, rshift, p_cap, c_cap,
-                     ((1 << 20) + F - 1) / F, BAGGED_BLOCK / F, BAGGED_BLOCK % F,
-                     ((1 << 20) + K - 1) / K);
+                     labels, B, F, K, T, n_nodes, n_leaves, g.rshift, p_cap, c_cap,
+                     g.f_magic, g.step_rows, g.step_cols, ((1 << 20) + K - 1) / K);
   return 0;
 }
 
@@ -393,19 +343,18 @@ int launch_bagged_forest_predict(const float* X, int B, int F, int K,
       n_nodes > (1 << 30) || n_leaves < 1 || n_leaves > n_nodes || max_tree_nodes < 1 ||
       max_tree_nodes > BAGGED_MAX_TREE_NODES)
     return -3;
-  int rshift = 0;
-  while ((1 << rshift) < R) ++rshift;
+  const ForestTileLaunch g = forest_tile_launch(B, F, R);
   int p_cap = max_tree_nodes < BAGGED_PREFIX_SLOTS ? max_tree_nodes : BAGGED_PREFIX_SLOTS;
   if (prefix_nodes >= 0 && prefix_nodes < p_cap) p_cap = prefix_nodes;
   // walks a thread has in a chunk of the fullest workgroup: U of them in flight
   const int rows = B < R ? B : R;
   int rp = 1;
   while (rp < rows) rp <<= 1;
-  const int walks = (rp * bagged_trees_per_chunk(rows, T, trees_per_chunk) + BAGGED_BLOCK - 1) /
-                    BAGGED_BLOCK;
+  const int walks = (rp * bagged_trees_per_chunk(rows, T, trees_per_chunk) + FOREST_BLOCK - 1) /
+                    FOREST_BLOCK;
 #define BAGGED_LAUNCH(U)                                                              \
   return launch_walks<U>(X, B, F, K, nodes, n_nodes, tree_first, T, leaf_values,      \
-                         n_leaves, p_cap, trees_per_chunk, probs, labels, rshift, stream)
+                         n_leaves, p_cap, trees_per_chunk, probs, labels, g, stream)
   if (walks >= 4) BAGGED_LAUNCH(4);   // eight in flight measured no faster (docs)
   if (walks >= 2) BAGGED_LAUNCH(2);
   BAGGED_LAUNCH(1);

@@ -24,6 +24,8 @@
 
 #include <hip/hip_runtime_api.h>
 
+#include "forest_limits.h"
+
 struct ForestNode {
   float thr;       // rd32(threshold): x <= t in fp64  <=>  x <= thr in fp32
   unsigned meta;   // feature 0..15 | left offset in the tree 16..30 | missing-left 31
@@ -31,28 +33,21 @@ struct ForestNode {
 };
 static_assert(sizeof(ForestNode) == 16, "one ds_read_b128 per visit");
 
-constexpr int FOREST_BLOCK = 256;
 // items (row, class) a thread may carry; a workgroup's R rows satisfy
 // R * K <= FOREST_BLOCK * FOREST_MAX_ITEMS
 constexpr int FOREST_MAX_ITEMS = 8;
-constexpr int FOREST_MAX_CLASSES = 32;
-constexpr int FOREST_MAX_FEATURES = 2048;
-constexpr int FOREST_MIN_ROWS = 4;          // rows per workgroup: a power of two,
-constexpr int FOREST_MAX_ROWS = 2048;       // FOREST_MIN_ROWS..FOREST_MAX_ROWS
+constexpr int FOREST_MAX_ROWS = 2048;       // the most rows per workgroup
 
 // The LDS carve, bytes from the base of dynamic LDS:
 //   [0, 32768)        the chunk's nodes, FOREST_CHUNK_NODES of them; after
 //                     the last chunk the workgroup's scores [R][K] fp64
 //   [32768, 33792)    the chunk's tree table: FOREST_CHUNK_TREES root offsets
 //   [33792, 34048)    the baseline, FOREST_MAX_CLASSES fp64
-//   [34048, ...)      the row tile [R][F | 1] fp32
-// The whole carve stays within FOREST_LDS_BUDGET so that two workgroups
-// share a CU's 160 KiB.
+//   [34048, ...)      the row tile [R][F | 1] fp32, within FOREST_LDS_BUDGET
 constexpr int FOREST_CHUNK_NODES = 2048;    // also the most nodes ONE tree may have
 constexpr int FOREST_CHUNK_TREES = 256;     // one table entry per thread
 constexpr int FOREST_LDS_TILE_OFF =
     FOREST_CHUNK_NODES * 16 + FOREST_CHUNK_TREES * 4 + FOREST_MAX_CLASSES * 8;
-constexpr int FOREST_LDS_BUDGET = 80 * 1024;
 constexpr int FOREST_TILE_BYTES = FOREST_LDS_BUDGET - FOREST_LDS_TILE_OFF;
 
 static_assert(FOREST_CHUNK_NODES % FOREST_BLOCK == 0 &&
@@ -61,25 +56,16 @@ static_assert(FOREST_CHUNK_NODES % FOREST_BLOCK == 0 &&
 static_assert(FOREST_BLOCK * FOREST_MAX_ITEMS * 8 <= FOREST_CHUNK_NODES * 16,
               "the final scores reuse the node area");
 static_assert(FOREST_CHUNK_NODES <= 1 << 15, "left offsets have 15 bits");
-static_assert(FOREST_MIN_ROWS * ((FOREST_MAX_FEATURES | 1) * 4) <= FOREST_TILE_BYTES,
+static_assert(FOREST_MIN_ROWS * (forest_row_stride(FOREST_MAX_FEATURES) * 4) <= FOREST_TILE_BYTES,
               "the widest row fits at the smallest R");
+static_assert(FOREST_MAX_FEATURES <= 1 << 16, "a node's feature has 16 bits");
 
-// row stride of the tile in dwords: odd, so that lanes reading different
-// features of different rows spread over the banks
-constexpr int forest_row_stride(int F) { return F | 1; }
-
-// Rows per workgroup for F features and K classes: the largest power of two
-// in FOREST_MIN_ROWS..FOREST_MAX_ROWS whose tile fits FOREST_TILE_BYTES and
-// whose R * K items fit FOREST_BLOCK * FOREST_MAX_ITEMS. 0: none (F or K out
-// of range).
+// Rows per workgroup for F features and K classes (forest_tile_rows): up to
+// FOREST_MAX_ROWS, the tile within FOREST_TILE_BYTES and the R * K items
+// within FOREST_BLOCK * FOREST_MAX_ITEMS.
 constexpr int forest_rows_per_wg(int F, int K) {
-  if (F < 1 || F > FOREST_MAX_FEATURES || K < 1 || K > FOREST_MAX_CLASSES) return 0;
-  int R = FOREST_MAX_ROWS;
-  while (R > FOREST_MIN_ROWS &&
-         ((long long)R * forest_row_stride(F) * 4 > FOREST_TILE_BYTES ||
-          R * K > FOREST_BLOCK * FOREST_MAX_ITEMS))
-    R >>= 1;
-  return R;
+  return forest_tile_rows(F, K, FOREST_MAX_ROWS, FOREST_TILE_BYTES,
+                          FOREST_BLOCK * FOREST_MAX_ITEMS);
 }
 static_assert(forest_rows_per_wg(64, 10) == 128 && forest_rows_per_wg(64, 32) == 64 &&
                   forest_rows_per_wg(5, 1) == 2048 && forest_rows_per_wg(300, 3) == 32 &&

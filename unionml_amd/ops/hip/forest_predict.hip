@@ -45,6 +45,7 @@
 #include <hip/hip_runtime.h>
 
 #include "forest.h"
+#include "forest_device.h"
 #include "tabular_launch.h"
 
 namespace {
@@ -61,7 +62,6 @@ struct ChunkRegs {
   int root;
 };
 static_assert(PRE == 8, "ChunkRegs names eight nodes");
-#define FOREST_EACH_NODE(X) X(0, n0) X(1, n1) X(2, n2) X(3, n3) X(4, n4) X(5, n5) X(6, n6) X(7, n7)
 
 // Start the loads of a chunk: `cnt` nodes from nodes[first] and the first
 // nodes of its trees, trees t0 .. t0 + 256. Nothing is waited for and
@@ -147,43 +147,8 @@ forest_predict_kernel(const float* __restrict__ X,            // [B][F]
   // the first leaf of every chunk waited for the NEXT chunk's loads
   if (tid < K) s_base[tid] = baseline[tid];
 
-  // ---- the row tile, while chunk 0 is in flight -------------------------------
-  // element e = row * F + col of the workgroup's contiguous block goes to
-  // s_rows[row * stride + col]; a thread takes e = tid, tid + 256, ... and
-  // moves (row, col) on by 256 elements with an add and a compare. Four
-  // loads are in flight before the first LDS store; they are unconditional
-  // (past the end they re-read the block's last element), the stores are
-  // predicated.
-  {
-    const float* __restrict__ Xw = X + (size_t)row0 * (size_t)F;
-    const int n = nrows * F;
-    int e = tid;
-    int row = (int)(((unsigned)tid * (unsigned)f_magic) >> 20);
-    int col = tid - row * F;
-    auto fetch = [&](float& v, int& at) {
-      v = Xw[e < n ? e : n - 1];
-      at = row * stride + col;
-      e += FOREST_BLOCK;
-      row += step_rows;
-      col += step_cols;
-      if (col >= F) {
-        col -= F;
-        ++row;
-      }
-    };
-    for (int e0 = tid; e0 - tid < n; e0 += 4 * FOREST_BLOCK) {
-      float v0, v1, v2, v3;
-      int a0, a1, a2, a3;
-      fetch(v0, a0);
-      fetch(v1, a1);
-      fetch(v2, a2);
-      fetch(v3, a3);
-      if (e0 < n) s_rows[a0] = v0;
-      if (e0 + FOREST_BLOCK < n) s_rows[a1] = v1;
-      if (e0 + 2 * FOREST_BLOCK < n) s_rows[a2] = v2;
-      if (e0 + 3 * FOREST_BLOCK < n) s_rows[a3] = v3;
-    }
-  }
+  // the row tile, while chunk 0 is in flight
+  forest_stage_rows(s_rows, X, row0, nrows, F, stride, f_magic, step_rows, step_cols, tid);
 
   store_chunk(regs, s_nodes, s_tab, b0, cnt, nt, tid);
   __syncthreads();
@@ -281,39 +246,22 @@ forest_predict_kernel(const float* __restrict__ X,            // [B][F]
   for (int i = tid; i < n_out; i += FOREST_BLOCK) out[i] = s_sc[i];
   for (int r = tid; r < nrows; r += FOREST_BLOCK) {
     const double* s = s_sc + r * K;
-    int best = 0;
-    if (K == 1) {
-      best = s[0] > 0.0 ? 1 : 0;
-    } else {
-      double top = s[0];
-      for (int k = 1; k < K; ++k) {
-        const double v = s[k];
-        if (v > top) {   // strict: ties stay with the lowest class
-          top = v;
-          best = k;
-        }
-      }
-    }
-    labels[row0 + r] = best;
+    labels[row0 + r] = K == 1 ? (s[0] > 0.0 ? 1 : 0) : forest_first_largest(s, K);
   }
 }
 
 template <int U>
 int launch_items(const float* X, int B, int F, int K, const ForestNode* nodes,
                  int n_nodes, const int* tree_first, int T, int tpc,
-                 const double* baseline, double* scores, int* labels, int rshift,
-                 hipStream_t stream) {
+                 const double* baseline, double* scores, int* labels,
+                 const ForestTileLaunch& g, hipStream_t stream) {
   if (ensure_dynamic_lds<forest_predict_kernel<U>>(FOREST_LDS_BUDGET) != 0) return -2;
-  const int R = 1 << rshift;
-  const int lds = FOREST_LDS_TILE_OFF + R * forest_row_stride(F) * 4;
-  const long long blocks = ((long long)B + R - 1) >> rshift;
   const int n_chunks = (T + tpc - 1) / tpc;
-  const int f_magic = ((1 << 20) + F - 1) / F;
-  hipLaunchKernelGGL(forest_predict_kernel<U>, dim3((unsigned)blocks),
-                     dim3(FOREST_BLOCK), lds, stream, X,
+  hipLaunchKernelGGL(forest_predict_kernel<U>, dim3(g.blocks), dim3(FOREST_BLOCK),
+                     FOREST_LDS_TILE_OFF + g.tile_bytes, stream, X,
                      reinterpret_cast<const uint4*>(nodes), tree_first, baseline,
-                     scores, labels, B, F, K, T, n_nodes, tpc, n_chunks, rshift,
-                     f_magic, FOREST_BLOCK / F, FOREST_BLOCK % F);
+                     scores, labels, B, F, K, T, n_nodes, tpc, n_chunks, g.rshift,
+                     g.f_magic, g.step_rows, g.step_cols);
   return 0;
 }
 
@@ -331,14 +279,13 @@ int launch_forest_predict(const float* X, int B, int F, int K,
   if (B < 1 || R == 0 || tpc == 0 || trees_per_chunk < 0 || n_nodes < 1 || T < 1 ||
       T > (1 << 30) || T % K != 0 || n_nodes < T || n_nodes > (1 << 30))
     return -3;
-  int rshift = 0;
-  while ((1 << rshift) < R) ++rshift;
+  const ForestTileLaunch g = forest_tile_launch(B, F, R);
   const int items = (R * K + FOREST_BLOCK - 1) / FOREST_BLOCK;
   switch (items) {
 #define FOREST_CASE(U)                                                            \
   case U:                                                                         \
     return launch_items<U>(X, B, F, K, nodes, n_nodes, tree_first, T, tpc,        \
-                           baseline, scores, labels, rshift, stream);
+                           baseline, scores, labels, g, stream);
     FOREST_CASE(1) FOREST_CASE(2) FOREST_CASE(3) FOREST_CASE(4)
     FOREST_CASE(5) FOREST_CASE(6) FOREST_CASE(7) FOREST_CASE(8)
 #undef FOREST_CASE

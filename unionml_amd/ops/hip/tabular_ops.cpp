@@ -1,7 +1,8 @@
 // Torch bindings for the CDNA4 tabular hot-path kernels
 // (tabular_kernels.hip, tabular_gen.hip, tabular_eval.hip, tabular_shuffle.hip,
 // forest_predict.hip, bagged_forest_predict.hip; launchers and layout
-// constants: tabular_launch.h, tabular_shuffle.h, forest.h, bagged_forest.h). All launches go to the current torch
+// constants: tabular_launch.h, tabular_shuffle.h, forest.h, bagged_forest.h,
+// forest_limits.h). All launches go to the current torch
 // stream so they compose with torch.cuda.graphs capture and RCCL work.
 
 #include <torch/extension.h>
@@ -660,90 +661,100 @@ torch::Tensor shuffle_perm_host(int64_t N, int64_t seed, int64_t t) {
 }
 
 // ---------------------------------------------------------------------------
-// forest inference (forest_predict.hip): scores and labels of a packed
-// gradient-boosted forest (forest.h)
+// forest inference (forest_predict.hip, bagged_forest_predict.hip): what the
+// two entry points check alike. Each checks its own fourth input (which
+// gives K) and its own ranges between the two halves.
 // ---------------------------------------------------------------------------
 
-void forest_predict(torch::Tensor X, torch::Tensor nodes, torch::Tensor tree_first,
-                    torch::Tensor baseline, int64_t max_tree_nodes,
-                    torch::Tensor scores, torch::Tensor labels,
-                    int64_t trees_per_chunk = 0) {
+namespace {
+
+// X [B][F] fp32, nodes [N][node_words] int32, tree_first [T + 1] int32 -> B, F, T
+std::array<int64_t, 3> check_forest_inputs(const torch::Tensor& X, const torch::Tensor& nodes,
+                                           int node_words, const torch::Tensor& tree_first) {
   const int64_t B = check_rows(X, torch::kFloat32, "X");
   const int64_t F = X.size(1);
   TORCH_CHECK(F <= FOREST_MAX_FEATURES, "X has ", F, " features, the row tile takes ",
               FOREST_MAX_FEATURES);
+  check(nodes, torch::kInt32, "nodes");
+  TORCH_CHECK(nodes.dim() == 2 && nodes.size(1) == node_words && nodes.size(0) >= 1 &&
+                  nodes.size(0) <= (1 << 30),
+              "nodes must be [1 <= N <= 2^30][", node_words, "] int32 (", 4 * node_words,
+              "-byte nodes), is ", nodes.sizes());
+  check(tree_first, torch::kInt32, "tree_first");
+  const int64_t T = tree_first.numel() - 1;
+  TORCH_CHECK(tree_first.dim() == 1 && T >= 1 && T <= nodes.size(0),
+              "tree_first must be [T + 1], 1 <= T <= the node count ", nodes.size(0),
+              ", is ", tree_first.sizes());
+  return {B, F, T};
+}
+
+// out [>= B][K] fp64 and labels [>= B] int32, sharing no storage with each
+// other or with an input
+void check_forest_outputs(const torch::Tensor& out, const char* out_name, int64_t B,
+                          int64_t K, const torch::Tensor& labels,
+                          std::initializer_list<Span> ins) {
+  check(out, torch::kFloat64, out_name);
+  TORCH_CHECK(out.dim() == 2 && out.size(0) >= B && out.size(1) == K, out_name,
+              " must be [>= ", B, "][", K, "], is ", out.sizes());
+  check_n(labels, torch::kInt32, "labels", B);
+  const Span outs[] = {span_of(out, out_name), span_of(labels, "labels")};
+  for (const Span& o : outs)
+    for (const Span& i : ins) check_disjoint(i, o);
+  check_disjoint(outs[0], outs[1]);
+}
+
+// a launcher's return code (tabular_launch.h's convention)
+void check_forest_rc(int rc, const char* op) {
+  TORCH_CHECK(rc != -2, op, ": could not raise the dynamic-LDS limit");
+  TORCH_CHECK(rc == 0, op, ": arguments outside the kernel's range");
+}
+
+}  // namespace
+
+// scores and labels of a packed gradient-boosted forest (forest.h)
+void forest_predict(torch::Tensor X, torch::Tensor nodes, torch::Tensor tree_first,
+                    torch::Tensor baseline, int64_t max_tree_nodes,
+                    torch::Tensor scores, torch::Tensor labels,
+                    int64_t trees_per_chunk = 0) {
+  const auto [B, F, T] = check_forest_inputs(X, nodes, 4, tree_first);
+  check_aligned16(nodes, "nodes");
   check(baseline, torch::kFloat64, "baseline");
   const int64_t K = baseline.numel();
   TORCH_CHECK(baseline.dim() == 1 && K >= 1 && K <= FOREST_MAX_CLASSES,
               "baseline must be [1 <= K <= ", FOREST_MAX_CLASSES, "], is ",
               baseline.sizes());
-  check(nodes, torch::kInt32, "nodes");
-  TORCH_CHECK(nodes.dim() == 2 && nodes.size(1) == 4 && nodes.size(0) >= 1 &&
-                  nodes.size(0) <= (1 << 30),
-              "nodes must be [1 <= N <= 2^30][4] int32 (16-byte nodes), is ",
-              nodes.sizes());
-  check_aligned16(nodes, "nodes");
-  check(tree_first, torch::kInt32, "tree_first");
-  const int64_t T = tree_first.numel() - 1;
-  TORCH_CHECK(tree_first.dim() == 1 && T >= 1 && T <= (1 << 30) && T % K == 0 &&
-                  T <= nodes.size(0),
-              "tree_first must be [T + 1], T a positive multiple of K = ", K,
-              " and at most the node count ", nodes.size(0), ", is ",
-              tree_first.sizes());
+  TORCH_CHECK(T % K == 0, "tree_first must be [T + 1], T a positive multiple of K = ", K,
+              ", is ", tree_first.sizes());
   TORCH_CHECK(max_tree_nodes >= 1 && max_tree_nodes <= FOREST_CHUNK_NODES,
               "max_tree_nodes must be 1..", FOREST_CHUNK_NODES,
               " (one tree must fit an LDS chunk), is ", max_tree_nodes);
   TORCH_CHECK(trees_per_chunk >= 0 && trees_per_chunk <= INT_MAX,
               "trees_per_chunk must be 0 (as many as fit) or positive, is ",
               trees_per_chunk);
-  check(scores, torch::kFloat64, "scores");
-  TORCH_CHECK(scores.dim() == 2 && scores.size(0) >= B && scores.size(1) == K,
-              "scores must be [>= ", B, "][", K, "], is ", scores.sizes());
-  check_n(labels, torch::kInt32, "labels", B);
-  const Span outs[] = {span_of(scores, "scores"), span_of(labels, "labels")};
-  const Span ins[] = {span_of(X, "X"), span_of(nodes, "nodes"),
-                      span_of(tree_first, "tree_first"), span_of(baseline, "baseline")};
-  for (const Span& o : outs)
-    for (const Span& i : ins) check_disjoint(i, o);
-  check_disjoint(outs[0], outs[1]);
+  check_forest_outputs(scores, "scores", B, K, labels,
+                       {span_of(X, "X"), span_of(nodes, "nodes"),
+                        span_of(tree_first, "tree_first"), span_of(baseline, "baseline")});
   const int rc = launch_forest_predict(
       X.data_ptr<float>(), (int)B, (int)F, (int)K,
       reinterpret_cast<const ForestNode*>(nodes.data_ptr()), (int)nodes.size(0),
       tree_first.data_ptr<int>(), (int)T, (int)max_tree_nodes, (int)trees_per_chunk,
       baseline.data_ptr<double>(), scores.data_ptr<double>(), labels.data_ptr<int>(),
       current_stream());
-  TORCH_CHECK(rc != -2, "forest_predict: could not raise the dynamic-LDS limit");
-  TORCH_CHECK(rc == 0, "forest_predict: arguments outside the kernel's range");
+  check_forest_rc(rc, "forest_predict");
 }
 
-// ---------------------------------------------------------------------------
-// bagged-forest inference (bagged_forest_predict.hip): mean leaf vectors and
-// labels of a packed random forest / extra-trees / decision tree
-// (bagged_forest.h)
-// ---------------------------------------------------------------------------
-
+// mean leaf vectors and labels of a packed random forest / extra-trees /
+// decision tree (bagged_forest.h)
 void bagged_forest_predict(torch::Tensor X, torch::Tensor nodes, torch::Tensor tree_first,
                            torch::Tensor leaf_values, int64_t max_tree_nodes,
                            torch::Tensor probs, torch::Tensor labels,
                            int64_t prefix_nodes = -1, int64_t trees_per_chunk = 0) {
-  const int64_t B = check_rows(X, torch::kFloat32, "X");
-  const int64_t F = X.size(1);
-  TORCH_CHECK(F <= BAGGED_MAX_FEATURES, "X has ", F, " features, the row tile takes ",
-              BAGGED_MAX_FEATURES);
-  check(nodes, torch::kInt32, "nodes");
-  TORCH_CHECK(nodes.dim() == 2 && nodes.size(1) == 2 && nodes.size(0) >= 1 &&
-                  nodes.size(0) <= (1 << 30),
-              "nodes must be [1 <= N <= 2^30][2] int32 (8-byte nodes), is ", nodes.sizes());
-  check(tree_first, torch::kInt32, "tree_first");
-  const int64_t T = tree_first.numel() - 1;
-  TORCH_CHECK(tree_first.dim() == 1 && T >= 1 && T <= nodes.size(0),
-              "tree_first must be [T + 1], 1 <= T <= the node count ", nodes.size(0),
-              ", is ", tree_first.sizes());
+  const auto [B, F, T] = check_forest_inputs(X, nodes, 2, tree_first);
   check(leaf_values, torch::kFloat64, "leaf_values");
   TORCH_CHECK(leaf_values.dim() == 2 && leaf_values.size(0) >= 1 &&
                   leaf_values.size(0) <= nodes.size(0) && leaf_values.size(1) >= 1 &&
-                  leaf_values.size(1) <= BAGGED_MAX_CLASSES,
-              "leaf_values must be [1 <= L <= N][1 <= K <= ", BAGGED_MAX_CLASSES, "], is ",
+                  leaf_values.size(1) <= FOREST_MAX_CLASSES,
+              "leaf_values must be [1 <= L <= N][1 <= K <= ", FOREST_MAX_CLASSES, "], is ",
               leaf_values.sizes());
   const int64_t K = leaf_values.size(1);
   TORCH_CHECK(max_tree_nodes >= 1 && max_tree_nodes <= BAGGED_MAX_TREE_NODES,
@@ -753,17 +764,10 @@ void bagged_forest_predict(torch::Tensor X, torch::Tensor nodes, torch::Tensor t
   TORCH_CHECK(trees_per_chunk >= 0 && trees_per_chunk <= INT_MAX,
               "trees_per_chunk must be 0 (as many as fit) or positive, is ",
               trees_per_chunk);
-  check(probs, torch::kFloat64, "probs");
-  TORCH_CHECK(probs.dim() == 2 && probs.size(0) >= B && probs.size(1) == K,
-              "probs must be [>= ", B, "][", K, "], is ", probs.sizes());
-  check_n(labels, torch::kInt32, "labels", B);
-  const Span outs[] = {span_of(probs, "probs"), span_of(labels, "labels")};
-  const Span ins[] = {span_of(X, "X"), span_of(nodes, "nodes"),
-                      span_of(tree_first, "tree_first"),
-                      span_of(leaf_values, "leaf_values")};
-  for (const Span& o : outs)
-    for (const Span& i : ins) check_disjoint(i, o);
-  check_disjoint(outs[0], outs[1]);
+  check_forest_outputs(probs, "probs", B, K, labels,
+                       {span_of(X, "X"), span_of(nodes, "nodes"),
+                        span_of(tree_first, "tree_first"),
+                        span_of(leaf_values, "leaf_values")});
   const int rc = launch_bagged_forest_predict(
       X.data_ptr<float>(), (int)B, (int)F, (int)K,
       reinterpret_cast<const BaggedNode*>(nodes.data_ptr()), (int)nodes.size(0),
@@ -771,8 +775,7 @@ void bagged_forest_predict(torch::Tensor X, torch::Tensor nodes, torch::Tensor t
       leaf_values.data_ptr<double>(), (int)leaf_values.size(0), (int)prefix_nodes,
       (int)trees_per_chunk, probs.data_ptr<double>(), labels.data_ptr<int>(),
       current_stream());
-  TORCH_CHECK(rc != -2, "bagged_forest_predict: could not raise the dynamic-LDS limit");
-  TORCH_CHECK(rc == 0, "bagged_forest_predict: arguments outside the kernel's range");
+  check_forest_rc(rc, "bagged_forest_predict");
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -792,8 +795,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         },
         "trees per chunk of a workgroup of bagged_forest_predict that holds `rows` rows",
         py::arg("rows"), py::arg("T"), py::arg("cap") = 0);
-  m.attr("BAGGED_MAX_CLASSES") = BAGGED_MAX_CLASSES;
-  m.attr("BAGGED_MAX_FEATURES") = BAGGED_MAX_FEATURES;
+  m.attr("BAGGED_MAX_CLASSES") = FOREST_MAX_CLASSES;
+  m.attr("BAGGED_MAX_FEATURES") = FOREST_MAX_FEATURES;
   m.attr("BAGGED_MAX_TREE_NODES") = BAGGED_MAX_TREE_NODES;
   m.attr("BAGGED_MAX_ROWS") = BAGGED_MAX_ROWS;
   m.attr("BAGGED_META_DIST_SHIFT") = BAGGED_META_DIST_SHIFT;
