@@ -24,6 +24,7 @@ ext = CUDAExtension(
         "unionml_amd/ops/hip/tabular_shuffle.hip",
         "unionml_amd/ops/hip/forest_predict.hip",
         "unionml_amd/ops/hip/bagged_forest_predict.hip",
+        "unionml_amd/ops/hip/forest_split_predict.hip",
     ],
     # editing a shared header rebuilds the extension
     depends=[
@@ -31,6 +32,7 @@ ext = CUDAExtension(
         "unionml_amd/ops/hip/forest.h",
         "unionml_amd/ops/hip/forest_device.h",
         "unionml_amd/ops/hip/forest_limits.h",
+        "unionml_amd/ops/hip/forest_split.h",
         "unionml_amd/ops/hip/tabular_common.h",
         "unionml_amd/ops/hip/tabular_gen_tiles.h",
         "unionml_amd/ops/hip/tabular_launch.h",

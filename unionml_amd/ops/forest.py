@@ -10,6 +10,15 @@ On a machine without a GPU the same packed arrays are walked by a plain
 vectorised fp64 traversal; on a GPU machine a missing extension is the usual
 ``KernelExtensionNotBuilt``.
 
+Every boosted forest is also packed for the **split walk** (``hip/forest_split.h``,
+the bagged 8-byte node and one fp64 per leaf): ``forest_split_walk_kernel``
+spreads (row, tree) walks over the whole device and ``forest_split_sum_kernel``
+adds their leaves in sklearn's order, so the bits are the same. It serves
+small batches, which the chunked kernel walks as one serial chain, and trees
+of more than 2,048 nodes, which the chunked kernel cannot hold
+(docs/kernels.md "Split walk"). ``walk=`` forces a path, ``walk_for(B)``
+tells the choice.
+
 ``BaggedForestPredictor`` does the same for ``RandomForest*``, ``ExtraTrees*``
 and single ``DecisionTree*`` / ``ExtraTree*`` estimators (the format of
 ``hip/bagged_forest.h``, ``bagged_forest_predict_kernel``): ``predict_proba``
@@ -38,6 +47,21 @@ TILE_BYTES = 80 * 1024 - (CHUNK_NODES * 16 + CHUNK_TREES * 4 + MAX_CLASSES * 8)
 NODE_DTYPE = np.dtype([("thr", "<f4"), ("meta", "<u4"), ("value", "<f8")])
 META_LEFT_SHIFT, META_MISSING_LEFT = 16, 1 << 31
 
+# the Python copy of hip/forest_split.h (a GPU test holds the two equal)
+SPLIT_PREFIX_SLOTS = 4096
+SPLIT_SLICE_TREES = 256
+SPLIT_WALK_ITEMS = 1024
+SPLIT_WG_MAX_ROWS = 256
+SPLIT_TILE_BYTES = 80 * 1024 - (SPLIT_PREFIX_SLOTS * 8 + 2 * SPLIT_SLICE_TREES * 4)
+SPLIT_SCRATCH_BYTES = 64 << 20      # leaf_rows of one launch; larger calls go in row blocks
+SPLIT_MAX_TREE_NODES = 1 << 20      # the bagged node's 20 bits of distance
+
+# Measured (profiles/r17_forest_split.md): the largest benchmarked batch at
+# which the split walk beats the chunked kernel on the digits forest by more
+# than the spread of the timing windows. walk=None takes the split walk up to
+# here.
+split_max_rows = 16384
+
 
 def rd32(t):
     """fp64 thresholds rounded to fp32 towards -inf: for every fp32 ``x``,
@@ -65,6 +89,21 @@ def rows_per_wg(n_features: int, n_scores: int) -> int:
     """Rows per workgroup of the boosted kernel: up to 2,048, rows x classes
     within 8 items a thread."""
     return _tile_rows(n_features, n_scores, MAX_ROWS, TILE_BYTES, BLOCK * MAX_ITEMS)
+
+
+def split_rows_per_wg(n_features: int) -> int:
+    """Rows per workgroup that the split walk's tile allows (a smaller batch
+    takes its own size rounded up to a power of two)."""
+    return _tile_rows(n_features, 1, SPLIT_WG_MAX_ROWS, SPLIT_TILE_BYTES, SPLIT_WG_MAX_ROWS)
+
+
+def split_trees_per_slice(rows: int, n_trees: int, cap: int = 0) -> int:
+    """Trees a workgroup of the split walk that holds ``rows`` rows owns."""
+    rp = 1
+    while rp < rows:
+        rp *= 2
+    n = max(1, min(SPLIT_WALK_ITEMS // rp, SPLIT_SLICE_TREES, n_trees))
+    return min(n, cap) if cap > 0 else n
 
 
 def _breadth_first(left, right, inner):
@@ -102,6 +141,46 @@ def _pack_tree(nodes):
     return out
 
 
+def _pack_split_tree(nodes, first_leaf_row):
+    """One sklearn boosted tree -> (bagged nodes, leaf values [leaves]),
+    renumbered breadth-first; leaves number the rows of leaf_values from
+    ``first_leaf_row`` in that order."""
+    order, new_of = _breadth_first(nodes["left"], nodes["right"],
+                                   ~nodes["is_leaf"].astype(bool))
+    src = nodes[order]
+    n = len(order)
+    leaf = src["is_leaf"].astype(bool)
+    dist = np.where(leaf, 0, new_of[np.where(leaf, 0, src["left"])] - np.arange(n))
+    assert np.all(leaf | (new_of[src["right"]] == np.arange(n) + dist + 1))
+    out = np.zeros(n, dtype=BAGGED_NODE_DTYPE)
+    out["thr"] = np.where(leaf, first_leaf_row + np.cumsum(leaf) - 1,
+                          rd32(src["num_threshold"]).view(np.uint32))
+    out["meta"] = (np.where(leaf, 0, src["feature_idx"]).astype(np.uint32)
+                   | np.where(~leaf & src["missing_go_to_left"].astype(bool),
+                              np.uint32(BAGGED_META_MISSING_LEFT), np.uint32(0))
+                   | (dist.astype(np.uint32) << BAGGED_META_DIST_SHIFT))
+    return out, np.ascontiguousarray(src["value"][leaf], dtype=np.float64)
+
+
+def _leaves_cpu(nodes, tree_first, X, t):
+    """leaf_values rows that the rows of X reach in tree t of a forest of
+    bagged nodes, by a vectorised walk."""
+    thr_bits, meta = nodes["thr"], nodes["meta"]
+    thr = thr_bits.view(np.float32)
+    rows = np.arange(X.shape[0])
+    idx = np.full(X.shape[0], int(tree_first[t]))
+    while True:
+        m = meta[idx]
+        dist = (m >> BAGGED_META_DIST_SHIFT).astype(np.int64)
+        x = X[rows, m & 0x7FF]
+        with np.errstate(invalid="ignore"):
+            go_left = np.where(np.isnan(x), (m & BAGGED_META_MISSING_LEFT) != 0,
+                               x <= thr[idx])
+        if not dist.any():
+            return thr_bits[idx].astype(np.int64)
+        idx = idx + np.where(dist > 0, dist + np.where(go_left, 0, 1), 0)
+
+
 class _PackedForest:
     """What the two predictors do alike: a packed forest's nodes and tree
     table on one device, the check of the rows, and the outputs around the
@@ -119,15 +198,23 @@ class _PackedForest:
         self.classes_ = None if classes is None else np.asarray(classes)
         self._nodes_np, self._first_np = nodes, tree_first
         self._ext = None
+        self._nodes = None
         if self.device.type == "cuda":
             self._ext = hip_ext(required=True)
-            words = nodes.dtype.itemsize // 4
-            self._nodes = torch.from_numpy(nodes.view("<i4").reshape(-1, words)).to(self.device)
+            self._nodes = self._upload_nodes(nodes)
             self._first = torch.from_numpy(tree_first).to(self.device)
 
     def _upload(self, array):
         """The predictor's own array on the device (None without a GPU)."""
         return None if self._ext is None else torch.from_numpy(array).to(self.device)
+
+    def _upload_nodes(self, nodes):
+        """Packed nodes as int32 words [N][words] on the device (None without
+        a GPU, or for a packing the forest does not have)."""
+        if self._ext is None or nodes is None:
+            return None
+        words = nodes.dtype.itemsize // 4
+        return self._upload(nodes.view("<i4").reshape(-1, words))
 
     @staticmethod
     def _refuse_beyond_limits(K, what, F, n_nodes):
@@ -161,21 +248,29 @@ class _PackedForest:
         if self._ext is not None:
             self._launch(X, out, labels, *caps)
             return out, labels
-        values, idx = self._host(X.numpy())
+        values, idx = self._host(X.numpy(), *caps)
         out.copy_(torch.from_numpy(values))
         labels.copy_(torch.from_numpy(idx.astype(np.int32)))
         return out, labels
 
 
 class ForestPredictor(_PackedForest):
-    """A packed forest on one device. Build with :meth:`from_sklearn`."""
+    """A packed forest on one device. Build with :meth:`from_sklearn`.
 
-    def __init__(self, nodes, tree_first, baseline, n_features, classes=None,
-                 identity_link=True, device=None):
+    ``nodes`` is the chunked kernel's 16-byte packing, or None when a tree
+    exceeds its 2,048 nodes; ``split_nodes`` / ``leaf_values`` are the split
+    walk's packing, which every forest has."""
+
+    def __init__(self, nodes, tree_first, baseline, n_features, split_nodes, leaf_values,
+                 classes=None, identity_link=True, device=None):
         super().__init__(nodes, tree_first, n_features, len(baseline), classes, device)
         self.rows_per_wg = rows_per_wg(self.n_features, self.n_scores)
+        self.split_rows_per_wg = split_rows_per_wg(self.n_features)
         self.identity_link = bool(identity_link)
         self._baseline_np, self._baseline = baseline, self._upload(baseline)
+        self._split_nodes_np, self._split_nodes = split_nodes, self._upload_nodes(split_nodes)
+        self._leaf_values_np, self._leaf_values = leaf_values, self._upload(leaf_values)
+        self._leaf_rows = None      # the split walk's scratch, grown on demand
 
     @classmethod
     def from_sklearn(cls, est, device=None):
@@ -186,34 +281,82 @@ class ForestPredictor(_PackedForest):
         if any(t["is_categorical"].any() for t in trees):
             raise ValueError("categorical splits are not supported by the forest kernel")
         largest = max(len(t) for t in trees)
-        if largest > CHUNK_NODES:
-            raise ValueError(f"a tree has {largest} nodes: one LDS chunk holds {CHUNK_NODES}")
-        nodes = np.concatenate([_pack_tree(t) for t in trees])
+        if largest > SPLIT_MAX_TREE_NODES:
+            raise ValueError(f"a tree has {largest} nodes: a child distance has 20 bits")
+        # the 16-byte packing needs every tree in one LDS chunk
+        nodes = (np.concatenate([_pack_tree(t) for t in trees]) if largest <= CHUNK_NODES
+                 else None)
+        packed, first_leaf_row = [], 0
+        for t in trees:
+            packed.append(_pack_split_tree(t, first_leaf_row))
+            first_leaf_row += len(packed[-1][1])
         tree_first = np.concatenate([[0], np.cumsum([len(t) for t in trees])]).astype(np.int32)
         # sklearn starts from zeros + baseline
         baseline = 0.0 + np.asarray(est._baseline_prediction, dtype=np.float64).reshape(-1)
         assert len(baseline) == K
-        return cls(nodes, tree_first, baseline, F, classes=getattr(est, "classes_", None),
+        return cls(nodes, tree_first, baseline, F, np.concatenate([p[0] for p in packed]),
+                   np.concatenate([p[1] for p in packed]),
+                   classes=getattr(est, "classes_", None),
                    identity_link=type(est._loss.link).__name__ == "IdentityLink",
                    device=device)
 
     # -- scoring ----------------------------------------------------------------
 
-    def _score(self, X, trees_per_chunk=0):
+    def walk_for(self, n_rows, trees_per_chunk=0):
+        """The path a call of ``n_rows`` rows takes when none is forced:
+        "split" for a forest without the 16-byte packing, "chunked" under a
+        ``trees_per_chunk`` cap, otherwise "split" up to ``split_max_rows``."""
+        if self._nodes_np is None:
+            return "split"
+        if trees_per_chunk > 0:
+            return "chunked"
+        return "split" if n_rows <= split_max_rows else "chunked"
+
+    def _score(self, X, trees_per_chunk=0, walk=None, prefix_nodes=-1, trees_per_slice=0):
         """-> (scores fp64 [B][K], class indices int32 [B]) on the device."""
-        return self._run(X, trees_per_chunk)
+        if walk is None:
+            walk = self.walk_for(X.shape[0] if hasattr(X, "shape") else len(X), trees_per_chunk)
+        if walk not in ("chunked", "split"):
+            raise ValueError(f'walk must be "chunked", "split" or None, is {walk!r}')
+        if walk == "chunked" and self._nodes_np is None:
+            raise ValueError(f"a tree has {self.max_tree_nodes} nodes: the chunked kernel "
+                             f"takes {CHUNK_NODES}, only the split walk serves this forest")
+        return self._run(X, walk, trees_per_chunk, prefix_nodes, trees_per_slice)
 
-    def _launch(self, X, scores, labels, trees_per_chunk):
-        self._ext.forest_predict(X, self._nodes, self._first, self._baseline,
-                                 self.max_tree_nodes, scores, labels, trees_per_chunk)
+    def _launch(self, X, scores, labels, walk, trees_per_chunk, prefix_nodes, trees_per_slice):
+        if walk == "chunked":
+            self._ext.forest_predict(X, self._nodes, self._first, self._baseline,
+                                     self.max_tree_nodes, scores, labels, trees_per_chunk)
+            return
+        # leaf_rows [T][rows] of one launch stays within SPLIT_SCRATCH_BYTES:
+        # rows are independent, so row blocks give the same bits
+        B, T = X.shape[0], self.n_trees
+        block = min(B, max(1, SPLIT_SCRATCH_BYTES // (4 * T)))
+        if self._leaf_rows is None or self._leaf_rows.numel() < T * block:
+            self._leaf_rows = torch.empty(T * block, dtype=torch.int32, device=self.device)
+        for b0 in range(0, B, block):
+            b1 = min(B, b0 + block)
+            self._ext.forest_split_predict(
+                X[b0:b1], self._split_nodes, self._first, self._leaf_values, self._baseline,
+                self.max_tree_nodes, self._leaf_rows, scores[b0:b1], labels[b0:b1],
+                prefix_nodes, trees_per_slice)
 
-    def _host(self, X):
-        s, _ = self._walk_cpu(X)
+    def _host(self, X, walk, *caps):
+        s = self._walk_cpu(X)[0] if walk == "chunked" else self._walk_split_cpu(X)
         return s, (s[:, 0] > 0) if self.n_scores == 1 else s.argmax(axis=1)   # first largest
 
+    def _walk_split_cpu(self, X):
+        """The split packing walked on the host, the trees' leaves added in
+        the sum kernel's order -> scores fp64 [B][K]."""
+        scores = np.tile(self._baseline_np, (X.shape[0], 1))
+        for t in range(self.n_trees):
+            leaves = _leaves_cpu(self._split_nodes_np, self._first_np, X, t)
+            scores[:, t % self.n_scores] += self._leaf_values_np[leaves]
+        return scores
+
     def _walk_cpu(self, X):
-        """The packed arrays walked on the host, tree by tree in the kernel's
-        order -> (scores fp64 [B][K], node visits, leaves included)."""
+        """The 16-byte packing walked on the host, tree by tree in the chunked
+        kernel's order -> (scores fp64 [B][K], node visits, leaves included)."""
         nodes, first, K = self._nodes_np, self._first_np, self.n_scores
         thr, meta, value = nodes["thr"], nodes["meta"], nodes["value"]
         B = X.shape[0]
@@ -236,29 +379,34 @@ class ForestPredictor(_PackedForest):
             scores[:, t % K] += value[idx]
         return scores, visits
 
-    def decision_function(self, X, trees_per_chunk=0):
+    def decision_function(self, X, trees_per_chunk=0, walk=None, prefix_nodes=-1,
+                          trees_per_slice=0):
         """Raw scores, fp64 ``[B][K]`` on the predictor's device: sklearn's
         ``decision_function`` (``predict`` for an identity-link regressor) bit
-        for bit. ``trees_per_chunk`` caps the trees per LDS chunk (tests)."""
-        return self._score(X, trees_per_chunk)[0]
+        for bit. ``walk`` forces the "chunked" kernel or the "split" walk
+        (None: :meth:`walk_for`). ``trees_per_chunk`` caps the chunked
+        kernel's trees per LDS chunk, ``prefix_nodes`` and ``trees_per_slice``
+        the split walk's LDS prefix and slice (tests)."""
+        return self._score(X, trees_per_chunk, walk, prefix_nodes, trees_per_slice)[0]
 
-    def predict(self, X, trees_per_chunk=0):
+    def predict(self, X, trees_per_chunk=0, walk=None, prefix_nodes=-1, trees_per_slice=0):
         """Classifier: labels by the raw-score argmax (ties to the lowest
         class; ``score > 0`` when binary) through ``classes_``, a numpy array.
         Regressor: the values, fp64 ``[B]`` on the device."""
+        if self.classes_ is None and not self.identity_link:
+            raise ValueError("predict() of a regressor with a non-identity link is not "
+                             "supported; decision_function() returns the raw scores")
+        scores, labels = self._score(X, trees_per_chunk, walk, prefix_nodes, trees_per_slice)
         if self.classes_ is None:
-            if not self.identity_link:
-                raise ValueError("predict() of a regressor with a non-identity link is not "
-                                 "supported; decision_function() returns the raw scores")
-            return self._score(X, trees_per_chunk)[0][:, 0]
-        return self.classes_[self._score(X, trees_per_chunk)[1].cpu().numpy()]
+            return scores[:, 0]
+        return self.classes_[labels.cpu().numpy()]
 
-    def predict_proba(self, X):
+    def predict_proba(self, X, walk=None):
         """softmax (sigmoid when binary) of the raw scores, with torch on the
         device; fp64 ``[B][n_classes]``."""
         if self.classes_ is None:
             raise ValueError("predict_proba() needs a classifier")
-        s = self.decision_function(X)
+        s = self.decision_function(X, walk=walk)
         if self.n_scores == 1:
             p = torch.sigmoid(s)
             return torch.cat([1.0 - p, p], dim=1)
@@ -377,26 +525,13 @@ class BaggedForestPredictor(_PackedForest):
                                         self.max_tree_nodes, probs, labels, prefix_nodes,
                                         trees_per_chunk)
 
-    def _host(self, X):
+    def _host(self, X, *caps):
         p = self._walk_cpu(X)
         return p, p.argmax(axis=1)   # first largest
 
     def _leaves_cpu(self, X, t):
         """leaf_values rows that the rows of X reach in tree t."""
-        thr_bits, meta = self._nodes_np["thr"], self._nodes_np["meta"]
-        thr = thr_bits.view(np.float32)
-        rows = np.arange(X.shape[0])
-        idx = np.full(X.shape[0], int(self._first_np[t]))
-        while True:
-            m = meta[idx]
-            dist = (m >> BAGGED_META_DIST_SHIFT).astype(np.int64)
-            x = X[rows, m & 0x7FF]
-            with np.errstate(invalid="ignore"):
-                go_left = np.where(np.isnan(x), (m & BAGGED_META_MISSING_LEFT) != 0,
-                                   x <= thr[idx])
-            if not dist.any():
-                return thr_bits[idx].astype(np.int64)
-            idx = idx + np.where(dist > 0, dist + np.where(go_left, 0, 1), 0)
+        return _leaves_cpu(self._nodes_np, self._first_np, X, t)
 
     def _walk_cpu(self, X):
         """The packed arrays walked on the host, the trees added in order and

@@ -1,8 +1,9 @@
 // Torch bindings for the CDNA4 tabular hot-path kernels
 // (tabular_kernels.hip, tabular_gen.hip, tabular_eval.hip, tabular_shuffle.hip,
-// forest_predict.hip, bagged_forest_predict.hip; launchers and layout
-// constants: tabular_launch.h, tabular_shuffle.h, forest.h, bagged_forest.h,
-// forest_limits.h). All launches go to the current torch
+// forest_predict.hip, bagged_forest_predict.hip, forest_split_predict.hip;
+// launchers and layout constants: tabular_launch.h, tabular_shuffle.h,
+// forest.h, bagged_forest.h, forest_split.h, forest_limits.h). All launches go
+// to the current torch
 // stream so they compose with torch.cuda.graphs capture and RCCL work.
 
 #include <torch/extension.h>
@@ -10,6 +11,7 @@
 
 #include "bagged_forest.h"
 #include "forest.h"
+#include "forest_split.h"
 #include "tabular_launch.h"
 #include "tabular_shuffle.h"
 
@@ -661,8 +663,8 @@ torch::Tensor shuffle_perm_host(int64_t N, int64_t seed, int64_t t) {
 }
 
 // ---------------------------------------------------------------------------
-// forest inference (forest_predict.hip, bagged_forest_predict.hip): what the
-// two entry points check alike. Each checks its own fourth input (which
+// forest inference (forest_predict.hip, bagged_forest_predict.hip,
+// forest_split_predict.hip): what the entry points check alike. Each checks its own fourth input (which
 // gives K) and its own ranges between the two halves.
 // ---------------------------------------------------------------------------
 
@@ -778,6 +780,53 @@ void bagged_forest_predict(torch::Tensor X, torch::Tensor nodes, torch::Tensor t
   check_forest_rc(rc, "bagged_forest_predict");
 }
 
+// scores and labels of a gradient-boosted forest in the split packing
+// (forest_split.h): (row, tree) walks into the caller's leaf_rows scratch,
+// then the ordered sum
+void forest_split_predict(torch::Tensor X, torch::Tensor nodes, torch::Tensor tree_first,
+                          torch::Tensor leaf_values, torch::Tensor baseline,
+                          int64_t max_tree_nodes, torch::Tensor leaf_rows,
+                          torch::Tensor scores, torch::Tensor labels,
+                          int64_t prefix_nodes = -1, int64_t trees_per_slice = 0) {
+  const auto [B, F, T] = check_forest_inputs(X, nodes, 2, tree_first);
+  check(leaf_values, torch::kFloat64, "leaf_values");
+  TORCH_CHECK(leaf_values.dim() == 1 && leaf_values.numel() >= 1 &&
+                  leaf_values.numel() <= nodes.size(0),
+              "leaf_values must be [1 <= L <= N], is ", leaf_values.sizes());
+  check(baseline, torch::kFloat64, "baseline");
+  const int64_t K = baseline.numel();
+  TORCH_CHECK(baseline.dim() == 1 && K >= 1 && K <= FOREST_MAX_CLASSES,
+              "baseline must be [1 <= K <= ", FOREST_MAX_CLASSES, "], is ",
+              baseline.sizes());
+  TORCH_CHECK(T % K == 0, "tree_first must be [T + 1], T a positive multiple of K = ", K,
+              ", is ", tree_first.sizes());
+  TORCH_CHECK(max_tree_nodes >= 1 && max_tree_nodes <= BAGGED_MAX_TREE_NODES,
+              "max_tree_nodes must be 1..", BAGGED_MAX_TREE_NODES, ", is ", max_tree_nodes);
+  TORCH_CHECK(prefix_nodes >= -1 && prefix_nodes <= INT_MAX,
+              "prefix_nodes must be -1 (as many as fit) or >= 0, is ", prefix_nodes);
+  TORCH_CHECK(trees_per_slice >= 0 && trees_per_slice <= INT_MAX,
+              "trees_per_slice must be 0 (by the launcher's rule) or positive, is ",
+              trees_per_slice);
+  check_n(leaf_rows, torch::kInt32, "leaf_rows", T * B);
+  const Span scratch = span_of(leaf_rows, "leaf_rows");
+  const std::initializer_list<Span> ins = {
+      span_of(X, "X"), span_of(nodes, "nodes"), span_of(tree_first, "tree_first"),
+      span_of(leaf_values, "leaf_values"), span_of(baseline, "baseline")};
+  check_forest_outputs(scores, "scores", B, K, labels, ins);
+  for (const Span& i : ins) check_disjoint(i, scratch);
+  check_disjoint(scratch, span_of(scores, "scores"));
+  check_disjoint(scratch, span_of(labels, "labels"));
+  const int rc = launch_forest_split_predict(
+      X.data_ptr<float>(), (int)B, (int)F, (int)K,
+      reinterpret_cast<const BaggedNode*>(nodes.data_ptr()), (int)nodes.size(0),
+      tree_first.data_ptr<int>(), (int)T, (int)max_tree_nodes,
+      leaf_values.data_ptr<double>(), (int)leaf_values.numel(),
+      baseline.data_ptr<double>(), (int)prefix_nodes, (int)trees_per_slice,
+      leaf_rows.data_ptr<int>(), scores.data_ptr<double>(), labels.data_ptr<int>(),
+      current_stream());
+  check_forest_rc(rc, "forest_split_predict");
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bagged_forest_predict", &bagged_forest_predict,
         "probs[b][k] = (the leaf vectors of trees 0, 1, ... added in order) / T (fp64, "
@@ -815,6 +864,29 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.attr("FOREST_CHUNK_NODES") = FOREST_CHUNK_NODES;
   m.attr("FOREST_CHUNK_TREES") = FOREST_CHUNK_TREES;
   m.attr("FOREST_MAX_FEATURES") = FOREST_MAX_FEATURES;
+  m.def("forest_split_predict", &forest_split_predict,
+        "forest_predict's scores and labels from the split packing: leaf_rows[t][b] = "
+        "the leaf of row b in tree t (one launch), then the ordered fp64 sum (a second)",
+        py::arg("X"), py::arg("nodes"), py::arg("tree_first"), py::arg("leaf_values"),
+        py::arg("baseline"), py::arg("max_tree_nodes"), py::arg("leaf_rows"),
+        py::arg("scores"), py::arg("labels"), py::arg("prefix_nodes") = -1,
+        py::arg("trees_per_slice") = 0);
+  m.def("forest_split_rows_per_wg",
+        [](int64_t F) { return forest_split_rows_per_wg((int)F); },
+        "rows per workgroup the split walk's tile allows (0: F out of range)",
+        py::arg("F"));
+  m.def("forest_split_trees_per_slice",
+        [](int64_t rows, int64_t T, int64_t cap) {
+          return forest_split_trees_per_slice((int)rows, (int)T, (int)cap);
+        },
+        "trees per slice of a split walk whose workgroups hold `rows` rows",
+        py::arg("rows"), py::arg("T"), py::arg("cap") = 0);
+  m.attr("SPLIT_PREFIX_SLOTS") = SPLIT_PREFIX_SLOTS;
+  m.attr("SPLIT_SLICE_TREES") = SPLIT_SLICE_TREES;
+  m.attr("SPLIT_WALK_ITEMS") = SPLIT_WALK_ITEMS;
+  m.attr("SPLIT_WG_MAX_ROWS") = SPLIT_WG_MAX_ROWS;
+  m.attr("SPLIT_TILE_BYTES") = SPLIT_TILE_BYTES;
+  m.attr("SPLIT_SCRATCH_BYTES") = (int64_t)SPLIT_SCRATCH_BYTES;
   m.def("shuffle_rows", &shuffle_rows,
         "Xs[i] = Xbf[src], ys[i] = y[src] (int32 labels), src = P(i; N, seed, "
         "t_dev[0]) the keyed permutation; perm_out[i] = src when given",
