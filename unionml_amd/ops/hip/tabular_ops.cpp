@@ -1,8 +1,9 @@
 // Torch bindings for the CDNA4 tabular hot-path kernels
 // (tabular_kernels.hip, tabular_gen.hip, tabular_eval.hip, tabular_shuffle.hip,
-// forest_predict.hip, bagged_forest_predict.hip, forest_split_predict.hip;
-// launchers and layout constants: tabular_launch.h, tabular_shuffle.h,
-// forest.h, bagged_forest.h, forest_split.h, forest_limits.h). All launches go
+// forest_predict.hip, bagged_forest_predict.hip, forest_split_predict.hip,
+// linear_logistic.hip; launchers and layout constants: tabular_launch.h,
+// tabular_shuffle.h, forest.h, bagged_forest.h, forest_split.h,
+// forest_limits.h, linear_logistic.h). All launches go
 // to the current torch
 // stream so they compose with torch.cuda.graphs capture and RCCL work.
 
@@ -12,6 +13,7 @@
 #include "bagged_forest.h"
 #include "forest.h"
 #include "forest_split.h"
+#include "linear_logistic.h"
 #include "tabular_launch.h"
 #include "tabular_shuffle.h"
 
@@ -827,7 +829,138 @@ void forest_split_predict(torch::Tensor X, torch::Tensor nodes, torch::Tensor tr
   check_forest_rc(rc, "forest_split_predict");
 }
 
+// ---------------------------------------------------------------------------
+// logistic regression (linear_logistic.hip)
+// ---------------------------------------------------------------------------
+
+namespace {
+
+// What both entry points take alike: X [B][F] fp32, W [Kc][F] fp64, b [Kc]
+// fp64 or absent, and the two test overrides -> B, F, Kc
+std::array<int64_t, 3> check_linear_inputs(const torch::Tensor& X, const torch::Tensor& W,
+                                           const c10::optional<torch::Tensor>& b,
+                                           int64_t rows_per_wg, int64_t max_wgs) {
+  const int64_t B = check_rows(X, torch::kFloat32, "X");
+  const int64_t F = X.size(1);
+  TORCH_CHECK(F <= LOGISTIC_MAX_FEATURES, "X has ", F, " features, the kernels take ",
+              LOGISTIC_MAX_FEATURES);
+  check(W, torch::kFloat64, "W");
+  TORCH_CHECK(W.dim() == 2 && W.size(0) >= 1 && W.size(0) <= LOGISTIC_MAX_CLASSES &&
+                  W.size(1) == F,
+              "W must be [1 <= Kc <= ", LOGISTIC_MAX_CLASSES, "][", F, "], is ", W.sizes());
+  if (b.has_value()) check_n(*b, torch::kFloat64, "b", W.size(0), true);
+  TORCH_CHECK(rows_per_wg == 0 || rows_per_wg == LOGISTIC_RB,
+              "rows_per_wg must be 0 or the compiled ", LOGISTIC_RB, ", is ", rows_per_wg);
+  TORCH_CHECK(max_wgs >= 0 && max_wgs <= INT_MAX,
+              "max_wgs must be 0 (twice the CU count) or positive, is ", max_wgs);
+  return {B, F, W.size(0)};
+}
+
+void check_linear_rc(int rc, const char* op) {
+  TORCH_CHECK(rc != -1, op, ": fewer slab rows than workgroups");
+  TORCH_CHECK(rc != -2, op, ": could not raise the dynamic-LDS limit");
+  TORCH_CHECK(rc == 0, op, ": arguments outside the kernel's range");
+}
+
+}  // namespace
+
+// (RB, workgroups) of a logistic_loss_grad / linear_predict call of N rows on
+// the current device: the slab rows a caller provides
+std::tuple<int64_t, int64_t> logistic_launch_shape_py(int64_t N, int64_t rows_per_wg,
+                                                      int64_t max_wgs) {
+  TORCH_CHECK(N >= 1 && N <= INT_MAX && max_wgs >= 0 && max_wgs <= INT_MAX,
+              "N must be 1..INT_MAX and max_wgs >= 0");
+  int rb = 0;
+  const int grid = logistic_launch_shape(N, (int)std::min<int64_t>(std::max<int64_t>(rows_per_wg, -1), INT_MAX),
+                                         (int)max_wgs, &rb);
+  TORCH_CHECK(grid >= 1, "rows_per_wg must be 0 or ", LOGISTIC_RB);
+  return {rb, grid};
+}
+
+// loss and gradient of sklearn's LinearModelLoss over (X, y, sw) at (W, b),
+// fp64: out = [gW row-major | gb when b is given | loss]
+void logistic_loss_grad(torch::Tensor X, torch::Tensor y,
+                        c10::optional<torch::Tensor> sample_weight, torch::Tensor W,
+                        c10::optional<torch::Tensor> b, double sw_sum, double l2,
+                        torch::Tensor slabs, torch::Tensor out, int64_t rows_per_wg = 0,
+                        int64_t max_wgs = 0) {
+  const auto [N, F, Kc] = check_linear_inputs(X, W, b, rows_per_wg, max_wgs);
+  check_n(y, torch::kInt32, "y", N, true);
+  const double* sw = opt_ptr<const double>(sample_weight, torch::kFloat64, "sample_weight");
+  TORCH_CHECK(sw == nullptr || sample_weight->numel() == N, "sample_weight must be [", N, "]");
+  TORCH_CHECK(sw_sum > 0.0 && l2 >= 0.0, "sw_sum must be positive and l2 non-negative");
+  const int64_t stride = logistic_slab_stride((int)Kc, (int)F);
+  check(slabs, torch::kFloat64, "slabs");
+  TORCH_CHECK(slabs.dim() == 2 && slabs.size(0) >= 1 && slabs.size(0) <= INT_MAX &&
+                  slabs.size(1) >= stride && slabs.size(1) <= INT_MAX,
+              "slabs must be [workgroups][>= ", stride, "], is ", slabs.sizes());
+  const int64_t n_out = Kc * F + (b.has_value() ? Kc : 0) + 1;
+  check_n(out, torch::kFloat64, "out", n_out);
+  std::vector<Span> ins{span_of(X, "X"), span_of(y, "y"), span_of(W, "W")};
+  if (b.has_value()) ins.push_back(span_of(*b, "b"));
+  if (sw != nullptr) ins.push_back(span_of(*sample_weight, "sample_weight"));
+  const Span outs[] = {span_of(out, "out"), span_of(slabs, "slabs")};
+  for (const Span& o : outs)
+    for (const Span& i : ins) check_disjoint(i, o);
+  check_disjoint(outs[0], outs[1]);
+  const int rc = launch_logistic_loss_grad(
+      X.data_ptr<float>(), y.data_ptr<int>(), sw, W.data_ptr<double>(),
+      b.has_value() ? b->data_ptr<double>() : nullptr, (int)N, (int)F, (int)Kc, sw_sum, l2,
+      slabs.data_ptr<double>(), (int)slabs.size(0), (int)slabs.size(1), out.data_ptr<double>(),
+      (int)rows_per_wg, (int)max_wgs, current_stream());
+  check_linear_rc(rc, "logistic_loss_grad");
+}
+
+// scores, probabilities and labels of a linear classifier (W, b)
+void linear_predict(torch::Tensor X, torch::Tensor W, c10::optional<torch::Tensor> b,
+                    torch::Tensor scores, c10::optional<torch::Tensor> probs,
+                    torch::Tensor labels, int64_t rows_per_wg = 0, int64_t max_wgs = 0) {
+  const auto [B, F, Kc] = check_linear_inputs(X, W, b, rows_per_wg, max_wgs);
+  const int64_t K = Kc == 1 ? 2 : Kc;
+  std::vector<Span> ins{span_of(X, "X"), span_of(W, "W")};
+  if (b.has_value()) ins.push_back(span_of(*b, "b"));
+  check(scores, torch::kFloat64, "scores");
+  TORCH_CHECK(scores.dim() == 2 && scores.size(0) >= B && scores.size(1) == Kc,
+              "scores must be [>= ", B, "][", Kc, "], is ", scores.sizes());
+  check_n(labels, torch::kInt32, "labels", B);
+  std::vector<Span> outs{span_of(scores, "scores"), span_of(labels, "labels")};
+  if (probs.has_value()) {
+    check(*probs, torch::kFloat64, "probs");
+    TORCH_CHECK(probs->dim() == 2 && probs->size(0) >= B && probs->size(1) == K,
+                "probs must be [>= ", B, "][", K, "], is ", probs->sizes());
+    outs.push_back(span_of(*probs, "probs"));
+  }
+  for (size_t o = 0; o < outs.size(); ++o) {
+    for (const Span& i : ins) check_disjoint(i, outs[o]);
+    for (size_t p = o + 1; p < outs.size(); ++p) check_disjoint(outs[o], outs[p]);
+  }
+  const int rc = launch_linear_predict(
+      X.data_ptr<float>(), W.data_ptr<double>(), b.has_value() ? b->data_ptr<double>() : nullptr,
+      (int)B, (int)F, (int)Kc, scores.data_ptr<double>(),
+      probs.has_value() ? probs->data_ptr<double>() : nullptr, labels.data_ptr<int>(),
+      (int)rows_per_wg, (int)max_wgs, current_stream());
+  check_linear_rc(rc, "linear_predict");
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("logistic_loss_grad", &logistic_loss_grad,
+        "out = [gW [Kc][F] | gb [Kc] when b is given | loss] of sklearn's LinearModelLoss "
+        "(multinomial over Kc classes, binomial at Kc == 1), fp64 on the matrix cores; the "
+        "same call gives the same bits",
+        py::arg("X"), py::arg("y"), py::arg("sample_weight"), py::arg("W"), py::arg("b"),
+        py::arg("sw_sum"), py::arg("l2"), py::arg("slabs"), py::arg("out"),
+        py::arg("rows_per_wg") = 0, py::arg("max_wgs") = 0);
+  m.def("linear_predict", &linear_predict,
+        "scores = X W^T + b (fp64); probs the softmax of a row, or [1 - s, s] at Kc == 1; "
+        "labels the first largest score, or score > 0 at Kc == 1",
+        py::arg("X"), py::arg("W"), py::arg("b"), py::arg("scores"), py::arg("probs"),
+        py::arg("labels"), py::arg("rows_per_wg") = 0, py::arg("max_wgs") = 0);
+  m.def("logistic_launch_shape", &logistic_launch_shape_py,
+        "(rows a block, workgroups) of a call of N rows on the current device",
+        py::arg("N"), py::arg("rows_per_wg") = 0, py::arg("max_wgs") = 0);
+  m.attr("LOGISTIC_MAX_CLASSES") = LOGISTIC_MAX_CLASSES;
+  m.attr("LOGISTIC_MAX_FEATURES") = LOGISTIC_MAX_FEATURES;
+  m.attr("LOGISTIC_RB") = LOGISTIC_RB;
   m.def("bagged_forest_predict", &bagged_forest_predict,
         "probs[b][k] = (the leaf vectors of trees 0, 1, ... added in order) / T (fp64, "
         "sklearn's bits at n_jobs=None); labels[b] = the first largest k",
