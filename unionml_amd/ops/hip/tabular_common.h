@@ -106,6 +106,67 @@ __device__ __forceinline__ float row_sum16(float x) {
   return x;
 }
 
+// Twelve row sums at once, one per lane instead of all twelve in every lane:
+// row_fold12(x) gives lane l the sum of x[row_fold_slot(l & 15)] over the 16
+// lanes of its row (a slot of 12 or more: a copy of slot 8 + (slot & 3)).
+// Each of row_sum16's four stages is a fold: a lane keeps one value of a
+// pair, sends the other to its stage partner and adds what it receives, so
+// every stage halves the registers, two selects and one DPP add per pair
+// (as compiled in the fused step: 37 VALU instructions against the 72 of
+// twelve row_sum16, profiles/r29_fused_row_segment.md).
+//
+// Bit for bit row_sum16(x[slot]): the same DPP controls, hence the same
+// partners and the same pairing tree (pairs, quads, eights, sixteen), and in
+// every add the lane's own partial sum is the left operand, as there. What a
+// lane keeps in stage K is decided by bit K of its slot, and the stage
+// partners are l^1, l^2, l^7 and l^15: the slot bits are chosen so that a
+// stage's partner differs in that stage's bit alone,
+//   slot bit 0 = b0^b2, bit 1 = b1^b2, bit 2 = b2^b3, bit 3 = b3
+// (b0..b3 the bits of l & 15), i.e. both partners always hold partial sums
+// of the same value. The keep/send predicates are compile-time lane masks
+// (a constant in a scalar register pair, v_cndmask reads it directly).
+// Every lane must be active.
+constexpr int row_fold_slot_c(int lr) {
+  return lr ^ ((lr & 4) ? 3 : 0) ^ ((lr & 8) >> 1);
+}
+__device__ __forceinline__ int row_fold_slot(int lr) { return row_fold_slot_c(lr); }
+
+constexpr unsigned long long row_fold_mask(int stage) {
+  unsigned long long m = 0;
+  for (int l = 0; l < 64; ++l)
+    if ((row_fold_slot_c(l & 15) >> stage) & 1) m |= 1ull << l;
+  return m;
+}
+constexpr bool row_fold_partners_ok() {
+  const int partner[4] = {1, 2, 7, 15};
+  for (int lr = 0; lr < 16; ++lr)
+    for (int k = 0; k < 4; ++k)
+      if ((row_fold_slot_c(lr) ^ row_fold_slot_c(lr ^ partner[k])) != (1 << k)) return false;
+  return true;
+}
+static_assert(row_fold_partners_ok(), "a stage's partner differs in that stage's slot bit only");
+
+// stage K of the fold: a where the lane's slot bit K is clear, b where it is
+// set, plus the same value's partial sum from the stage partner
+template <int STAGE, int CTRL>
+__device__ __forceinline__ float row_fold_pair(float a, float b) {
+  const bool up = __builtin_amdgcn_inverse_ballot_w64(row_fold_mask(STAGE));
+  const float keep = up ? b : a;
+  const float send = up ? a : b;
+  return keep + dpp_row_f32<CTRL>(send);
+}
+
+__device__ __forceinline__ float row_fold12(const float (&x)[12]) {
+  float p[6], q[3];
+  #pragma unroll
+  for (int j = 0; j < 6; ++j) p[j] = row_fold_pair<0, 0xB1>(x[2 * j], x[2 * j + 1]);
+  #pragma unroll
+  for (int j = 0; j < 3; ++j) q[j] = row_fold_pair<1, 0x4E>(p[2 * j], p[2 * j + 1]);
+  const float lo8 = row_fold_pair<2, 0x141>(q[0], q[1]);
+  const float hi4 = q[2] + dpp_row_f32<0x141>(q[2]);   // the odd one: a plain stage
+  return row_fold_pair<3, 0x140>(lo8, hi4);
+}
+
 // The two operands of a fold across lanes l and l ^ D, D = 16 or 32 (the
 // lane-group axis of an MFMA D tile), without the LDS crossbar:
 // v_permlane16_swap exchanges the odd rows of its first operand with the

@@ -561,6 +561,10 @@ __device__ __forceinline__ void chunk_fwd_bwd(
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 
   // ---- fwd2: L^T = W2T @ B(Hs);  D: c = lg*4+r, row = wrow+lr --------------
+  // the lane's twelve bias-gradient terms, db1 of h = mt*16+lg*4+r in
+  // [mt*4 + r] and db2 of c = lg*4+r in [8 + r]: summed over the wave's 16
+  // rows in ONE fold behind dH (row_fold12)
+  float bsum[12];
   {
     f32x4 acc[1] = {{0.f, 0.f, 0.f, 0.f}};
     const bf16x8 a = *(const bf16x8*)&L.W2T[lr][lg * 8];
@@ -585,24 +589,18 @@ __device__ __forceinline__ void chunk_fwd_bwd(
       if (valid && c == label) loss_acc = -(logit[0][r] - m - logs) * invBtot;
     }
     store_bf16x4(&L.DLs[row][lg * 4], db2_acc);
-    // reduce db2/loss over the 16 row-lanes (lr bits) first, then ONE
-    // plain store per (wave, class) into this wave's partial row: the
+    // db2 waits in bsum for the fold behind dH. The loss is reduced here,
+    // with every lane active (DPP reads its row neighbours' registers):
+    // over the 16 row-lanes (lr bits), then over the four lg groups (lane
+    // bits 4, 5), then ONE plain store into this wave's partial row. The
     // waves are summed in fixed order below, so the step is reproducible
-    // bit for bit (float LDS atomics landed in arrival order). All five
-    // reductions run first, with every lane active (DPP reads its row
-    // neighbours' registers); the predicated stores follow in one block.
+    // bit for bit (float LDS atomics landed in arrival order).
     #pragma unroll
-    for (int r = 0; r < 4; ++r) db2_acc[r] = row_sum16(db2_acc[r]);
+    for (int r = 0; r < 4; ++r) bsum[8 + r] = db2_acc[r];
     loss_acc = row_sum16(loss_acc);
-    // loss_acc now holds the 16-row sum within this lg quarter; fold
-    // the four lg groups (lane bits 4,5) too, then one store per wave
     loss_acc = group_sum<16>(loss_acc);
     loss_acc = group_sum<32>(loss_acc);
-    if (lr == 0) {
-      #pragma unroll
-      for (int r = 0; r < 4; ++r) L.part[wave * PART + HID + lg * 4 + r] = db2_acc[r];
-      if (l == 0) L.part[wave * PART + HID + CPAD] = loss_acc;
-    }
+    if (l == 0) L.part[wave * PART + HID + CPAD] = loss_acc;
   }
   // NO __syncthreads here either: dH reads only this wave's rows of
   // DLs. Cross-wave consumers (dW2 over all rows of Hs and DLs) wait at the
@@ -626,23 +624,34 @@ __device__ __forceinline__ void chunk_fwd_bwd(
       // row-major, the lane's four consecutive h of its row as one store
       store_bf16x4(&L.DHs[wrow + lr][mt * 16 + lg * 4], db1_acc[mt]);
     }
-    // db1[h]: sum this row-block's contribution across the 16 lr lanes.
-    // All eight reductions first, no branch between them, then the
-    // predicated stores in one block.
+    // db1[h] and db2[c]: this row-block's contribution summed across the 16
+    // lr lanes, all twelve in one fold, every lane active. Bit for bit
+    // twelve row_sum16 (tabular_common.h), but a lane comes out with ONE of
+    // the sums, number `slot` of bsum, and stores it itself: one store per
+    // lane into this wave's partial row instead of twelve from lane lr == 0.
+    // Slots 0..7 are db1 (PART offset mt*16 + lg*4 + r), 8..11 db2 (HID +
+    // lg*4 + r): both are (slot>>2)*16 + lg*4 + (slot&3), HID being 32.
+    static_assert(HID == 32, "bsum slot -> PART offset");
     #pragma unroll
     for (int mt = 0; mt < HID / 16; ++mt) {
       #pragma unroll
-      for (int r = 0; r < 4; ++r) db1_acc[mt][r] = row_sum16(db1_acc[mt][r]);
+      for (int r = 0; r < 4; ++r) bsum[mt * 4 + r] = db1_acc[mt][r];
     }
-    if (lr == 0) {
-      #pragma unroll
-      for (int mt = 0; mt < HID / 16; ++mt) {
-        #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          L.part[wave * PART + mt * 16 + lg * 4 + r] = db1_acc[mt][r];
-        }
-      }
-    }
+    const float sum = row_fold12(bsum);
+    const int slot = row_fold_slot(lr);
+    if (slot < 12) L.part[wave * PART + (slot >> 2) * 16 + lg * 4 + (slot & 3)] = sum;
+  }
+  // dW1's X operand, read AHEAD of the barrier: Xs has been complete since
+  // the caller's barrier in front of this function and nothing above writes
+  // it, so the four transposed reads need not wait for the other waves. The
+  // waves that reach the barrier early (two share a SIMD, one of them loses
+  // the arbitration) read while they would stand idle, and behind the barrier
+  // every wave has four operand reads in front of its MFMAs, not eight.
+  // Every lane gets here: EXEC is full (tr_read_k8).
+  bf16x8 xb[ROWS / 32];
+  #pragma unroll
+  for (int ks = 0; ks < ROWS / 32; ++ks) {
+    xb[ks] = tr_read_k8<XS, ROWS / 32, IN / 16>(L.Xs, ks, wave >> 1, l);
   }
   // DHs + per-wave partials complete; and every wave's Hs and DLs rows, which
   // dW2 reads across waves
@@ -669,23 +678,23 @@ __device__ __forceinline__ void chunk_fwd_bwd(
 
   // ---- dW1^T += DH^T @ B(X^T): wave tile (ht = w&1, it = w>>1). K is the
   // batch row, the row axis of DHs and Xs: transposed reads (tr_read_k8,
-  // tabular_common.h). Every lane of every wave gets here: EXEC is full. -----
+  // tabular_common.h); the X operand is xb, read in front of the barrier.
+  // Every lane of every wave gets here: EXEC is full. ------------------------
   {
-    const int ht = wave & 1, it = wave >> 1;
+    const int ht = wave & 1;
     // all the reads, then the MFMAs: left in one loop the compiler keeps each
     // k-step's reads behind the previous k-step's MFMA, four LDS round trips
     // in a row
-    bf16x8 a[ROWS / 32], b[ROWS / 32];
+    bf16x8 a[ROWS / 32];
     #pragma unroll
     for (int ks = 0; ks < ROWS / 32; ++ks) {
       a[ks] = tr_read_k8<DHS, ROWS / 32, HID / 16>(L.DHs, ks, ht, l);
-      b[ks] = tr_read_k8<XS, ROWS / 32, IN / 16>(L.Xs, ks, it, l);
     }
     __builtin_amdgcn_sched_barrier(0);
     f32x4 acc = acc_io.dW1;
     #pragma unroll
     for (int ks = 0; ks < ROWS / 32; ++ks) {
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[ks], b[ks], acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[ks], xb[ks], acc, 0, 0, 0);
     }
     acc_io.dW1 = acc;
   }
@@ -708,8 +717,9 @@ __device__ __forceinline__ void chunk_fwd_bwd(
     acc_io.dW2 = acc;
   }
   STAMP(st, ST_MFMA);
-  // chunk arrays free for reuse: Xs above all, which dW1 has just read and
-  // the caller's next store_x_chunk refills
+  // chunk arrays free for reuse: DHs, Hs and DLs, which the GEMMs above have
+  // just read, and Xs (last read in front of the barrier above), which the
+  // caller's next store_x_chunk refills
   if constexpr (!SINGLE) __syncthreads();
 }
 
@@ -971,10 +981,9 @@ mlp_step_fused_kernel(// the seven arguments the prologue's vector loads need
   // single-chunk form: no barrier at its end. Each wave goes from its last
   // MFMA straight to its slab stores below; the next workgroup barrier is
   // the publish barrier, and the chunk arrays are reused only behind it
-  // (the Adam-state prefetch into Xs). Xs is read until each wave's dW1,
-  // its second-to-last or last GEMM: the publish barrier is behind every
-  // wave's dW1, so the prefetch cannot overwrite rows a slower wave still
-  // has to read.
+  // (the Adam-state prefetch into Xs). Every wave's last read of Xs, dW1's
+  // X operand, stands in front of the chunk's own barrier (the second), so
+  // the prefetch cannot overwrite rows a slower wave still has to read.
   chunk_fwd_bwd<true>(L, L.b1s, L.b2s, chunk_label(xr), xr.valid, invBtot, acc,
                       bias_sum STAMPS_ARG);
 #endif
