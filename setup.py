@@ -26,6 +26,7 @@ ext = CUDAExtension(
         "unionml_amd/ops/hip/bagged_forest_predict.hip",
         "unionml_amd/ops/hip/forest_split_predict.hip",
         "unionml_amd/ops/hip/linear_logistic.hip",
+        "unionml_amd/ops/hip/linear_gram.hip",
     ],
     # editing a shared header rebuilds the extension
     depends=[
@@ -34,6 +35,7 @@ ext = CUDAExtension(
         "unionml_amd/ops/hip/forest_device.h",
         "unionml_amd/ops/hip/forest_limits.h",
         "unionml_amd/ops/hip/forest_split.h",
+        "unionml_amd/ops/hip/linear_gram.h",
         "unionml_amd/ops/hip/linear_logistic.h",
         "unionml_amd/ops/hip/tabular_common.h",
         "unionml_amd/ops/hip/tabular_gen_tiles.h",

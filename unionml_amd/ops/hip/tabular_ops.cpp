@@ -1,9 +1,9 @@
 // Torch bindings for the CDNA4 tabular hot-path kernels
 // (tabular_kernels.hip, tabular_gen.hip, tabular_eval.hip, tabular_shuffle.hip,
 // forest_predict.hip, bagged_forest_predict.hip, forest_split_predict.hip,
-// linear_logistic.hip; launchers and layout constants: tabular_launch.h,
-// tabular_shuffle.h, forest.h, bagged_forest.h, forest_split.h,
-// forest_limits.h, linear_logistic.h). All launches go
+// linear_logistic.hip, linear_gram.hip; launchers and layout constants:
+// tabular_launch.h, tabular_shuffle.h, forest.h, bagged_forest.h, forest_split.h,
+// forest_limits.h, linear_logistic.h, linear_gram.h). All launches go
 // to the current torch
 // stream so they compose with torch.cuda.graphs capture and RCCL work.
 
@@ -13,6 +13,7 @@
 #include "bagged_forest.h"
 #include "forest.h"
 #include "forest_split.h"
+#include "linear_gram.h"
 #include "linear_logistic.h"
 #include "tabular_launch.h"
 #include "tabular_shuffle.h"
@@ -942,7 +943,88 @@ void linear_predict(torch::Tensor X, torch::Tensor W, c10::optional<torch::Tenso
   check_linear_rc(rc, "linear_predict");
 }
 
+// ---------------------------------------------------------------------------
+// ridge regression (linear_gram.hip)
+// ---------------------------------------------------------------------------
+
+// (row slices, doubles of one slice of the slabs, rows of the moment slabs) of
+// a ridge_gram call on the current device: what a caller allocates
+std::tuple<int64_t, int64_t, int64_t> ridge_launch_shape_py(int64_t N, int64_t F, int64_t T,
+                                                            int64_t row_slices) {
+  TORCH_CHECK(N >= 1 && N <= INT_MAX, "N must be 1..INT_MAX, is ", N);
+  TORCH_CHECK(F >= 1 && F <= RIDGE_MAX_FEATURES, "F must be 1..", RIDGE_MAX_FEATURES, ", is ", F);
+  TORCH_CHECK(T >= 1 && T <= RIDGE_MAX_TARGETS, "T must be 1..", RIDGE_MAX_TARGETS, ", is ", T);
+  TORCH_CHECK(row_slices >= 0 && row_slices <= GRAM_MAX_SLICES,
+              "row_slices must be 0 (by the launcher's rule) or 1..", GRAM_MAX_SLICES, ", is ",
+              row_slices);
+  int slices = 0, moment_rows = 0;
+  long long stride = 0;
+  const int rc = ridge_launch_shape(N, (int)F, (int)T, (int)row_slices, &slices, &stride,
+                                    &moment_rows);
+  TORCH_CHECK(rc == 0, "ridge_launch_shape: no device to size the launch for");
+  return {slices, stride, moment_rows};
+}
+
+// mean = [mu | ybar], A = Xc^T S Xc + alpha I, Xy = Xc^T S Yc in fp64
+void ridge_gram(torch::Tensor X, torch::Tensor Y, c10::optional<torch::Tensor> sample_weight,
+                double alpha, bool center, torch::Tensor mean, torch::Tensor A,
+                torch::Tensor Xy, torch::Tensor slabs, torch::Tensor moment_slabs,
+                int64_t row_slices = 0) {
+  const int64_t N = check_rows(X, torch::kFloat32, "X");
+  const int64_t F = X.size(1);
+  TORCH_CHECK(F <= RIDGE_MAX_FEATURES, "X has ", F, " features, the kernels take ",
+              RIDGE_MAX_FEATURES);
+  check(Y, torch::kFloat64, "Y");
+  TORCH_CHECK(Y.dim() == 2 && Y.size(0) == N && Y.size(1) >= 1 &&
+                  Y.size(1) <= RIDGE_MAX_TARGETS,
+              "Y must be [", N, "][1 <= T <= ", RIDGE_MAX_TARGETS, "], is ", Y.sizes());
+  const int64_t T = Y.size(1);
+  const double* sw = opt_ptr<const double>(sample_weight, torch::kFloat64, "sample_weight");
+  TORCH_CHECK(sw == nullptr || (sample_weight->dim() == 1 && sample_weight->numel() == N),
+              "sample_weight must be [", N, "]");
+  TORCH_CHECK(alpha >= 0.0, "alpha must be non-negative, is ", alpha);
+  const auto [S, stride, moment_rows] = ridge_launch_shape_py(N, F, T, row_slices);
+  check_n(mean, torch::kFloat64, "mean", F + T, true);
+  check(A, torch::kFloat64, "A");
+  TORCH_CHECK(A.dim() == 2 && A.size(0) == F && A.size(1) == F, "A must be [", F, "][", F,
+              "], is ", A.sizes());
+  check(Xy, torch::kFloat64, "Xy");
+  TORCH_CHECK(Xy.dim() == 2 && Xy.size(0) == F && Xy.size(1) == T, "Xy must be [", F, "][", T,
+              "], is ", Xy.sizes());
+  check_n(slabs, torch::kFloat64, "slabs", S * stride);
+  check_n(moment_slabs, torch::kFloat64, "moment_slabs",
+          moment_rows * gram_moment_stride((int)F, (int)T));
+  std::vector<Span> ins{span_of(X, "X"), span_of(Y, "Y")};
+  if (sw != nullptr) ins.push_back(span_of(*sample_weight, "sample_weight"));
+  const Span outs[] = {span_of(mean, "mean"), span_of(A, "A"), span_of(Xy, "Xy"),
+                       span_of(slabs, "slabs"), span_of(moment_slabs, "moment_slabs")};
+  for (size_t o = 0; o < std::size(outs); ++o) {
+    for (const Span& i : ins) check_disjoint(i, outs[o]);
+    for (size_t p = o + 1; p < std::size(outs); ++p) check_disjoint(outs[o], outs[p]);
+  }
+  const int rc = launch_ridge_gram(
+      X.data_ptr<float>(), Y.data_ptr<double>(), sw, (int)N, (int)F, (int)T, alpha,
+      center ? 1 : 0, mean.data_ptr<double>(), A.data_ptr<double>(), Xy.data_ptr<double>(),
+      slabs.data_ptr<double>(), (long long)slabs.numel(), moment_slabs.data_ptr<double>(),
+      (int)std::min<int64_t>(moment_slabs.numel() / gram_moment_stride((int)F, (int)T), INT_MAX),
+      (int)row_slices, current_stream());
+  check_linear_rc(rc, "ridge_gram");
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("ridge_gram", &ridge_gram,
+        "mean = [mu | ybar] (weighted column means, zeros without center), A = Xc^T S Xc + "
+        "alpha I, Xy = Xc^T S Yc, fp64 on the matrix cores from an fp32 X; A is symmetric bit "
+        "for bit and the same call gives the same bits",
+        py::arg("X"), py::arg("Y"), py::arg("sample_weight"), py::arg("alpha"),
+        py::arg("center"), py::arg("mean"), py::arg("A"), py::arg("Xy"), py::arg("slabs"),
+        py::arg("moment_slabs"), py::arg("row_slices") = 0);
+  m.def("ridge_launch_shape", &ridge_launch_shape_py,
+        "(row slices, doubles of one slice of the slabs, rows of the moment slabs [F + T + 1]) "
+        "of a ridge_gram call on the current device",
+        py::arg("N"), py::arg("F"), py::arg("T"), py::arg("row_slices") = 0);
+  m.attr("RIDGE_MAX_FEATURES") = RIDGE_MAX_FEATURES;
+  m.attr("RIDGE_MAX_TARGETS") = RIDGE_MAX_TARGETS;
   m.def("logistic_loss_grad", &logistic_loss_grad,
         "out = [gW [Kc][F] | gb [Kc] when b is given | loss] of sklearn's LinearModelLoss "
         "(multinomial over Kc classes, binomial at Kc == 1), fp64 on the matrix cores; the "

@@ -18,6 +18,13 @@ probabilities and labels in one launch); ``LinearPredictor.from_sklearn(est)``
 and ``device_linear(est)`` serve a fitted sklearn ``LogisticRegression``.
 Without a GPU the same classes run a numpy fp64 implementation of the same
 formulas; on a GPU machine a missing extension is ``KernelExtensionNotBuilt``.
+
+``DeviceRidge`` is sklearn's ``Ridge(solver="cholesky")`` with the centred,
+weighted Gram matrix and moment matrix formed on the device by ``ridge_gram``
+(``hip/linear_gram.hip``) and scipy's ``solve(A, Xy, assume_a="pos")`` on the
+host (docs/kernels.md "Ridge regression"). ``LinearRegressionPredictor`` and
+``device_linear_regressor(est)`` score a fitted ``Ridge`` or
+``LinearRegression`` through ``linear_predict``.
 """
 
 import warnings
@@ -30,6 +37,9 @@ from unionml_amd.ops import hip_ext
 # the Python copy of hip/linear_logistic.h
 MAX_CLASSES = 32
 MAX_FEATURES = 1 << 20
+# the Python copy of hip/linear_gram.h
+RIDGE_MAX_FEATURES = 4096
+RIDGE_MAX_TARGETS = 32
 
 
 def _refuse_beyond_limits(n_classes, n_features):
@@ -355,4 +365,190 @@ def device_linear(est):
     cache = getattr(est, "_unionml_linear", None)
     if cache is None:
         cache = est._unionml_linear = _LinearCache()
+    return cache.get(est)
+
+
+# ---- ridge regression ---------------------------------------------------------------
+
+
+def _refuse_beyond_ridge_limits(n_features, n_targets):
+    if not 1 <= n_features <= RIDGE_MAX_FEATURES:
+        raise ValueError(f"{n_features} features: the Gram kernel takes 1..{RIDGE_MAX_FEATURES}")
+    if not 1 <= n_targets <= RIDGE_MAX_TARGETS:
+        raise ValueError(f"{n_targets} targets: the kernels take 1..{RIDGE_MAX_TARGETS}")
+
+
+def gram_numpy(X, Y, sw, alpha, center):
+    """The Gram kernel's formulas in numpy fp64 -> (mean [F + T], A [F][F],
+    Xy [F][T])."""
+    w = np.ones(len(X)) if sw is None else sw
+    if center:
+        mu, ybar = w @ X / w.sum(), w @ Y / w.sum()
+    else:
+        mu, ybar = np.zeros(X.shape[1]), np.zeros(Y.shape[1])
+    Xc, Yc = X - mu, Y - ybar
+    A = (Xc * w[:, None]).T @ Xc
+    A[np.diag_indices_from(A)] += alpha
+    return np.concatenate([mu, ybar]), A, (Xc * w[:, None]).T @ Yc
+
+
+class LinearRegressionPredictor:
+    """A linear regressor (``coef`` [T][F] or [F], ``intercept`` [T], a scalar
+    or None) on one device: ``predict`` is ``X coef^T + intercept`` in fp64
+    through ``linear_predict``. Build with :meth:`from_sklearn`."""
+
+    def __init__(self, coef, intercept, device=None):
+        coef = np.asarray(coef, dtype=np.float64)
+        self.single = coef.ndim == 1           # sklearn's shapes for a 1-D y
+        coef = np.ascontiguousarray(np.atleast_2d(coef))
+        if coef.ndim != 2 or not 1 <= coef.shape[1] <= MAX_FEATURES:
+            raise ValueError(f"coef is {coef.shape}: [T][F] or [F] with 1..{MAX_FEATURES} features")
+        if not 1 <= coef.shape[0] <= RIDGE_MAX_TARGETS:
+            raise ValueError(f"{coef.shape[0]} targets: the kernels take 1..{RIDGE_MAX_TARGETS}")
+        if device is None:
+            device = "cuda" if torch.cuda.is_available() else "cpu"
+        self.device = torch.device(device)
+        self.n_targets, self.n_features = coef.shape
+        self._W_np = coef
+        self._b_np = (None if intercept is None else np.array(
+            np.broadcast_to(np.asarray(intercept, dtype=np.float64), (self.n_targets,))))
+        self._ext = None
+        if self.device.type == "cuda":
+            self._ext = hip_ext(required=True)
+            self._W = torch.from_numpy(coef).to(self.device)
+            self._b = None if self._b_np is None else torch.from_numpy(self._b_np).to(self.device)
+
+    @classmethod
+    def from_sklearn(cls, est, device=None):
+        from sklearn.linear_model import LinearRegression, Ridge
+
+        if not isinstance(est, (Ridge, LinearRegression)) or not hasattr(est, "coef_"):
+            raise TypeError(f"{type(est).__name__} is no fitted Ridge or LinearRegression")
+        return cls(est.coef_, est.intercept_, device=device)
+
+    def predict(self, X):
+        """fp64 ``[B]`` (a 1-D ``coef``) or ``[B][T]``, a numpy array."""
+        X = _rows(X, self.n_features).to(self.device)
+        B = X.shape[0]
+        scores = torch.empty(B, self.n_targets, dtype=torch.float64, device=self.device)
+        if B > 0 and self._ext is not None:
+            # the classifier's kernel as it is: its labels go to a throwaway buffer
+            labels = torch.empty(B, dtype=torch.int32, device=self.device)
+            self._ext.linear_predict(X, self._W, self._b, scores, None, labels, 0, 0)
+        elif B > 0:
+            z = X.numpy().astype(np.float64) @ self._W_np.T
+            scores.copy_(torch.from_numpy(z if self._b_np is None else z + self._b_np))
+        out = scores.cpu().numpy()
+        return out[:, 0] if self.single else out
+
+
+class DeviceRidge:
+    """sklearn's ``Ridge(solver="cholesky")`` with the Gram matrix on the
+    device: ``ridge_gram`` forms ``A = Xc^T S Xc + alpha I`` and
+    ``Xy = Xc^T S Yc`` in fp64 from the fp32 X, the host solves
+    ``scipy.linalg.solve(A, Xy, assume_a="pos")``, sklearn's own call. The
+    primal form is used for N < F too. X is held in fp32 (see the module
+    docstring)."""
+
+    def __init__(self, alpha=1.0, fit_intercept=True, device=None):
+        if not alpha >= 0:
+            raise ValueError(f"alpha must be non-negative, is {alpha}")
+        self.alpha, self.fit_intercept = float(alpha), bool(fit_intercept)
+        if device is None:
+            device = "cuda" if torch.cuda.is_available() else "cpu"
+        self.device = torch.device(device)
+        self._predictor = None
+
+    def _gram(self, X, Y, sw, row_slices):
+        """-> (mean, A, Xy) as numpy fp64, from the device or from numpy."""
+        if self.device.type != "cuda":
+            return gram_numpy(X.numpy().astype(np.float64), Y, sw, self.alpha, self.fit_intercept)
+        ext, dev = hip_ext(required=True), self.device
+        (N, F), T = X.shape, Y.shape[1]
+        with torch.cuda.device(dev):
+            slices, stride, moment_rows = ext.ridge_launch_shape(N, F, T, row_slices)
+            f64 = dict(dtype=torch.float64, device=dev)
+            mean, A, Xy = torch.empty(F + T, **f64), torch.empty(F, F, **f64), torch.empty(F, T, **f64)
+            ext.ridge_gram(X.to(dev), torch.from_numpy(Y).to(dev),
+                           None if sw is None else torch.from_numpy(sw).to(dev), self.alpha,
+                           self.fit_intercept, mean, A, Xy,
+                           torch.empty(slices * stride, **f64),
+                           torch.empty(moment_rows, F + T + 1, **f64), row_slices)
+            return mean.cpu().numpy(), A.cpu().numpy(), Xy.cpu().numpy()
+
+    def fit(self, X, y, sample_weight=None, row_slices=0):
+        """One ``ridge_gram`` call and one host solve. ``row_slices`` overrides
+        the launcher's choice (tests)."""
+        import scipy.linalg
+
+        X = _rows(X)
+        y = np.asarray(y, dtype=np.float64)
+        N, F = X.shape
+        if y.ndim not in (1, 2) or len(y) != N or N == 0:
+            raise ValueError(f"y must be [{N}] or [{N}][T] with at least one row, is {y.shape}")
+        Y = np.ascontiguousarray(y.reshape(N, -1))
+        T = Y.shape[1]
+        _refuse_beyond_ridge_limits(F, T)
+        sw = None
+        if sample_weight is not None:
+            sw = np.ascontiguousarray(sample_weight, dtype=np.float64)
+            if sw.shape != (N,) or not (sw >= 0).all() or not sw.sum() > 0:
+                raise ValueError(f"sample_weight must be [{N}], non-negative with a positive sum")
+        mean, A, Xy = self._gram(X, Y, sw, row_slices)
+        try:
+            coef = scipy.linalg.solve(A, Xy, assume_a="pos", overwrite_a=True).T
+        except np.linalg.LinAlgError as exc:
+            raise ValueError("the Gram matrix is singular (alpha = 0 on dependent columns?): "
+                             "sklearn's SVD fallback is not served") from exc
+        intercept = mean[F:] - coef @ mean[:F] if self.fit_intercept else np.zeros(T)
+        if y.ndim == 1:
+            self.coef_ = coef[0].copy()
+            self.intercept_ = np.float64(intercept[0]) if self.fit_intercept else 0.0
+        else:
+            self.coef_ = np.ascontiguousarray(coef)
+            self.intercept_ = intercept if self.fit_intercept else 0.0
+        self.n_features_in_ = F
+        self._predictor = LinearRegressionPredictor(
+            self.coef_, self.intercept_ if self.fit_intercept else None, device=self.device)
+        return self
+
+    def predict(self, X):
+        if self._predictor is None:
+            raise ValueError("this DeviceRidge is not fitted yet")
+        return self._predictor.predict(X)
+
+    def to_sklearn(self):
+        """A plain ``sklearn.linear_model.Ridge`` carrying the fitted
+        attributes: what artifacts save and the serving code loads."""
+        from sklearn.linear_model import Ridge
+
+        if self._predictor is None:
+            raise ValueError("this DeviceRidge is not fitted yet")
+        est = Ridge(alpha=self.alpha, fit_intercept=self.fit_intercept, solver="cholesky")
+        est.coef_ = self.coef_.copy()
+        est.intercept_ = (self.intercept_.copy() if isinstance(self.intercept_, np.ndarray)
+                          else self.intercept_)
+        est.n_features_in_, est.n_iter_, est.solver_ = self.n_features_in_, None, "cholesky"
+        return est
+
+
+class _LinearRegressionCache(_LinearCache):
+    """:class:`_LinearCache` for a fitted ``Ridge`` or ``LinearRegression``."""
+
+    def __reduce__(self):
+        return (_LinearRegressionCache, ())
+
+    def get(self, est):
+        if self.coef is not est.coef_ or self.intercept is not est.intercept_:
+            self.predictor = LinearRegressionPredictor.from_sklearn(est)
+            self.coef, self.intercept = est.coef_, est.intercept_
+        return self.predictor
+
+
+def device_linear_regressor(est):
+    """The device predictor of a fitted sklearn ``Ridge`` or
+    ``LinearRegression``, built once per fit and kept on the estimator."""
+    cache = getattr(est, "_unionml_linear", None)
+    if cache is None:
+        cache = est._unionml_linear = _LinearRegressionCache()
     return cache.get(est)
